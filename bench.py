@@ -23,7 +23,12 @@ Run:  python bench.py [--gpus N --steps K --warmup W --workload NAME --method fu
       N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N, or plain
       `python bench.py --gpus N`, which starts the N ranks itself (torch.distributed.run as a child
       process, before any GPU call) and exits with its status.
-The line of the default workload also carries a "batched" block for BASELINE config 3
+A plain run does what the headline needs and no more: set up, W warmup solves (and the resident
+server's priming), the K timed steps, the result line (its roofline comes from the timed launches'
+own events).  --dump-outputs DIR then writes what the last timed step computed as DIR/<name>.npy.
+--full adds everything else: the BASELINE-config blocks, the fp64 side line, the HBM-roofline side
+measurement and the CPU baselines (--no-sharded / --no-f64 / --no-hbm / --no-cpu drop one of them).
+With --full the line of the default workload also carries a "batched" block for BASELINE config 3
 (fourrooms4096, independent per GPU) and a "sharded" block per BASELINE multi-GPU config
 (lava65536, doorkey65536): the global batch sharded over the N ranks (at N = 1 the direct solve),
 updates/s over the whole job, ms per solve, sweeps, at N > 1 the collectives per solve, and at
@@ -74,6 +79,31 @@ GEN_WORKLOADS = {
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: the .npy files of one run stay under this in all
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> array, what a caller of the timed path receives from its
+    last step) as path/<name>.npy, float32 (float64 stays float64); rank r > 0 of a multi-GPU run
+    writes <name>.rank<r>.npy.  The files hold at most DUMP_MAX_BYTES in all: every array gets a
+    share of that budget in proportion to its size, and one over its share is cut to a fixed sample
+    of its rows (first axis; sorted indices drawn with numpy's default_rng(0), so two runs with the
+    same arguments keep the same rows)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(v)) for k, v in arrays.items()}
+    out_dt = {k: np.float64 if v.dtype == np.float64 else np.float32 for k, v in arrays.items()}
+    size = {k: v.size * np.dtype(out_dt[k]).itemsize for k, v in arrays.items()}  # bytes as written
+    total = sum(size.values())
+    budget = DUMP_MAX_BYTES - 4096 * len(arrays)  # the .npy headers
+    for name, a in arrays.items():
+        if total > budget and a.size:
+            rows = max(1, int(budget * (size[name] / total)) // max(1, size[name] // len(a)))
+            if rows < len(a):
+                a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 and rank else "") + ".npy"),
+                np.ascontiguousarray(a, dtype=out_dt[name]))
 
 
 def step_bytes_per_env_step(view: int) -> int:
@@ -339,7 +369,14 @@ def main():
     ap.add_argument("--no-hbm", action="store_true", help="skip the HBM-roofline side measurement")
     ap.add_argument("--no-f64", action="store_true", help="skip the fp64 (parity-mode) side measurement")
     ap.add_argument("--no-sharded", action="store_true", help="skip the sharded lava65536 / doorkey65536 blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the BASELINE-config blocks, the fp64 side "
+                         "line, the HBM-roofline side measurement and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -421,7 +458,7 @@ def main():
             reducer_box.append(Reducer(timing=True))  # built once; its stream carries the shards' launches
         return reducer_box[0]
 
-    def run_workload(name, dtype=None, split_events=False):
+    def run_workload(name, dtype=None, split_events=False, dump=False):
         spec = WORKLOADS[name]
         t_gen = time.perf_counter()
         cells, (lo, hi) = make_cells(spec, rank, world)
@@ -434,7 +471,7 @@ def main():
             n_all = spec["global_grids"] if spec["sharded"] else spec["per_gpu"] * world
             fresh = [make_cells(spec, rank, world, seed_offset=(i + 1) * n_all)[0] for i in range(FRESH_SETS)]
         m = measure(wargs, dtype or args.dtype, cells, local, dist, red_dev, get_reducer() if sharded else None, sharded,
-                    split_events=split_events, fresh=fresh)
+                    split_events=split_events, fresh=fresh, dump=dump)
         return spec, cells, (lo, hi), sharded, m
 
     # the BASELINE configs 3-5 beside the default line (every rank takes part), run BEFORE the
@@ -442,7 +479,8 @@ def main():
     # lone-grid server starts (the driver measured 11.3 us per solve first-in-process vs 9.3 us for
     # the fp64 line after these blocks, round 3); the headline's priming rule still applies
     blocks, batched = {}, {}
-    if args.workload == "empty16" and not args.no_sharded and args.method == "fused" and args.mapping == "cell":
+    if (args.full and args.workload == "empty16" and not args.no_sharded and args.method == "fused"
+            and args.mapping == "cell"):
         # BASELINE configs 3-5 beside the headline: FourRooms x 4096 per GPU (independent batches),
         # LavaS11N5 / DoorKey-16 x 65536 sharded over the N ranks; each with the oracle timed on a
         # bounded sample of the same grids at N = 1
@@ -486,7 +524,10 @@ def main():
     # MGDP_BENCH_SPLIT_EVENTS=1 (rehearsal knob, tools/gpu_shard_prof.sh): the main line's region
     # without per-launch events too, as the blocks beside the headline run it
     spec, cells, (lo, hi), sharded, m = run_workload(args.workload,
-                                                     split_events=os.environ.get("MGDP_BENCH_SPLIT_EVENTS") == "1")
+                                                     split_events=os.environ.get("MGDP_BENCH_SPLIT_EVENTS") == "1",
+                                                     dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"], rank, world)
     if rank != 0:  # the fp64 side line and the CPU baselines are N = 1 only
         if dist is not None:
             dist.barrier()
@@ -532,16 +573,16 @@ def main():
         out["batched"] = batched
     if blocks:
         out["sharded"] = blocks
-    if args.dtype == "f32" and world == 1 and not args.no_f64:
+    if args.full and args.dtype == "f32" and world == 1 and not args.no_f64:
         m64 = measure(args, "f64", cells, local, dist, red_dev, get_reducer() if sharded else None, sharded)
         out["f64"] = {"value": m64["upd_total"] / m64["elapsed_max"], "unit": "updates/s",
                       "ms_per_step": m64["elapsed_max"] * 1000.0 / args.steps, "sweeps": int(m64["sweeps"][-1]),
                       "kernel": m64["info"]["kernel"],
                       "note": "same workload and steps in fp64 (parity mode: bit-exact with the fp64 oracle)"}
 
-    if world == 1 and not args.no_hbm and args.workload == "empty16":
+    if args.full and world == 1 and not args.no_hbm and args.workload == "empty16":
         out["roofline_hbm"] = hbm_side_measurement(args)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         out["host"] = host_info()
         lone = bool(spec.get("distinct"))
         out["cpu_baseline"] = cpu_baseline(cells, vi_info["model"], args.gamma, args.tol, args.dtype, args.cpu_budget,
@@ -646,8 +687,10 @@ def compulsory_bytes_per_solve(info, tsize, method, sweeps):
     return B * (compulsory_bytes_per_sweep(S, HW, tsize) * sweeps + S * tsize + HW + S)
 
 
-def measure(args, dtype, cells, local, dist, red_dev, reducer, sharded, split_events=False, fresh=None):
+def measure(args, dtype, cells, local, dist, red_dev, reducer, sharded, split_events=False, fresh=None, dump=False):
     """W warmup solves, then K timed solves (barrier + synchronize on both sides, max over ranks).
+    dump: the result also holds "outputs", what the last timed solve gave its caller (V, pi and the
+    sweep count), read back after the region.
     split_events (the BASELINE-config blocks beside the headline): the timed region runs without the
     library's per-launch HIP events -- on a batched solve they cost 6-9 us of host time per launch
     (tools/probe_timing_cost.py, profiles/r04_tcost/) -- and the launch durations for the roofline
@@ -792,6 +835,9 @@ def measure(args, dtype, cells, local, dist, red_dev, reducer, sharded, split_ev
                                       "gap": round((t0 - pstamps[-1]) * 1e6, 2),
                                       "solves": [round(x, 2) for x in us[:-2]], "vi_sync": round(us[-2], 2),
                                       "dev_sync": round(us[-1], 2), "region": round(elapsed * 1e6, 2)}}))
+    outputs = None
+    if dump:  # the last timed solve's results, before anything else solves on this handle
+        outputs = {"V": vi.values(), "pi": vi.policy(), "sweeps": np.array([sweeps[-1]], np.float64)}
     red_region = None
     if reducer is not None:  # the region's protocol counters (the events pass below adds its own)
         red_region = (reducer.calls, reducer.host_reads, reducer.wall_s)
@@ -912,7 +958,7 @@ def measure(args, dtype, cells, local, dist, red_dev, reducer, sharded, split_ev
             "events_in_region": not split,
             "executed": executed,
             "launches": launches, "primed": primed, "timed_primed": PRIME_RELAUNCH if info["persistent"] else 0,
-            "info": info, "collectives": collectives, "latency": lat, "fresh": fresh_out}
+            "info": info, "collectives": collectives, "latency": lat, "fresh": fresh_out, "outputs": outputs}
 
 
 def host_cores() -> int:
@@ -1071,6 +1117,10 @@ def step_bench(args, rank, world, local, dist, red_dev):
     kern_s = ev0.elapsed_time(ev1) / 1000.0
     assert int(status.max().item()) == 0, "step kernel reported an error status"
     elapsed_max, steps_total = _max_over_ranks(dist, red_dev, elapsed, float(B) * args.steps)
+    if args.dump_outputs:  # what the last timed step returned
+        dump_outputs(args.dump_outputs, {"obs": obs.cpu().numpy(), "direction": dirn.cpu().numpy(),
+                                         "reward": rew.cpu().numpy(), "terminated": term.cpu().numpy(),
+                                         "truncated": trunc.cpu().numpy(), "status": status.cpu().numpy()}, rank, world)
     out = None
     if rank == 0:
         bpe = step_bytes_per_env_step(V)
@@ -1092,7 +1142,7 @@ def step_bench(args, rank, world, local, dist, red_dev):
                          "alg_bytes_per_env_step": bpe,
                          "timing": "one event pair on the launch stream around the K launches / K"},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = step_cpu_baseline(venv, acts, args.cpu_budget)
     venv.close()
     return out
@@ -1143,6 +1193,9 @@ def gen_bench(args, rank, world, local, dist, red_dev):
     elapsed, kern_s = _timed_launches(args, launch, dist, stream)
     assert int(agent[:, 2].min().item()) >= 0, "generator reported a placement failure"
     elapsed_max, total = _max_over_ranks(dist, red_dev, elapsed, float(B) * args.steps)
+    if args.dump_outputs:  # what the last timed launch wrote
+        dump_outputs(args.dump_outputs, {"enc": enc.cpu().numpy(), "cells": cells.cpu().numpy(),
+                                         "agent": agent.cpu().numpy()}, rank, world)
     out = None
     if rank == 0:
         bpg = W * H * 3 + H * W + 12  # written per grid: encoding + type codes + agent
@@ -1163,7 +1216,7 @@ def gen_bench(args, rank, world, local, dist, red_dev):
                          "regime": "integer RNG / rejection-loop latency bound (one thread per seed); "
                                    "HBM carries only the output"},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = gen_cpu_baseline(env, args.cpu_budget)
     return out
 

@@ -49,6 +49,7 @@ class FakeVI:
     def solve(self, last=False):
         self._check()
         r = oracle.value_iteration(0, self._cells, tol=self._tol, dtype=self._dtype)
+        self._last = r
         self._solves += 1
         if self._own is None:
             self._own = np.array([oracle.value_iteration(0, c, tol=self._tol, dtype=self._dtype)["sweeps"]
@@ -69,6 +70,14 @@ class FakeVI:
     def grid_sweeps(self):
         self._check()
         return self._own
+
+    def values(self):
+        self._check()
+        return self._last["V"]
+
+    def policy(self):
+        self._check()
+        return self._last["pi"]
 
     def close(self):
         self._open = False
@@ -188,3 +197,42 @@ def test_compact_line_fits_the_driver_tail(bench):
     assert fr["v"] == pytest.approx(2.6e13 * 2.718281828, rel=1e-3)
     assert fr["x"] == pytest.approx(2.6e13 * 1.7182818, rel=1e-3)
     assert {"c1", "c16", "f1", "f16", "xf", "valu", "k", "ms"} <= set(fr)
+
+
+def test_measure_dump_holds_the_last_timed_solve(bench):
+    # --dump-outputs: measure() hands back what the last timed solve gave its caller, and only on request
+    from minigrid_dynamicprogramming_amd import make
+
+    env = make("MiniGrid-FourRooms-v0")
+    cells = np.stack([np.ascontiguousarray(env.generate(seed=s)[0][..., 0].T) for s in range(4)])
+    m = bench.measure(_args("fourrooms4096"), "f32", cells, 0, None, None, None, False, dump=True)
+    o = oracle.value_iteration(0, cells, dtype="f32")
+    assert set(m["outputs"]) == {"V", "pi", "sweeps"}
+    assert np.array_equal(m["outputs"]["V"], o["V"]) and np.array_equal(m["outputs"]["pi"], o["pi"])
+    assert m["outputs"]["sweeps"].tolist() == [o["sweeps"]] and len(m["sweeps"]) == 3
+    assert bench.measure(_args("fourrooms4096"), "f32", cells, 0, None, None, None, False)["outputs"] is None
+
+
+def test_dump_outputs_files_and_seeded_sample(bench, tmp_path, monkeypatch):
+    rng = np.random.default_rng(7)
+    arrays = {"V": rng.random((300, 64), np.float32), "pi": rng.integers(0, 7, (300, 64)).astype(np.int8),
+              "dv": rng.random(5), "sweeps": np.float64(29)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == set(arrays)
+    assert got["V"].dtype == np.float32 and got["pi"].dtype == np.float32 and got["dv"].dtype == np.float64
+    assert np.array_equal(got["V"], arrays["V"]) and np.array_equal(got["pi"], arrays["pi"])
+    assert np.array_equal(got["dv"], arrays["dv"]) and got["sweeps"].tolist() == [29.0]
+    # over the budget: every file is cut to whole rows, the same ones on every run, in their order
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 4096 + 40000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays, rank=1, world=2)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["V.rank1.npy", "dv.rank1.npy", "pi.rank1.npy", "sweeps.rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 4 * 4096 + 40000
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    v = np.load(tmp_path / "b" / "V.rank1.npy")
+    assert 0 < len(v) < 300 and v.shape[1:] == (64,)
+    rows = [int(np.flatnonzero((arrays["V"] == r).all(axis=1))[0]) for r in v]
+    assert rows == sorted(set(rows))

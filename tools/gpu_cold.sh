@@ -12,7 +12,7 @@ mkdir -p $OUT
 ls -l /sys/class/drm/card*/device/pp_dpm_sclk > $OUT/sysfs.txt 2>&1 || true
 MGDP_LIB=exp_diag/trace/libmgdp.so timeout -k 10 120 python -u tools/probe_cold.py --out $OUT/cold_trace.json > $OUT/cold_trace.log 2> $OUT/cold_trace.err || { echo "probe failed"; tail -20 $OUT/cold_trace.err; exit 1; }
 cat $OUT/cold_trace.log; grep "serve trace" $OUT/cold_trace.err | head -60
-MGDP_BENCH_STAMPS=1 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench1.json 2> $OUT/bench1.err || { echo "bench failed"; tail $OUT/bench1.err; exit 1; }
+MGDP_BENCH_STAMPS=1 timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench1.json 2> $OUT/bench1.err || { echo "bench failed"; tail $OUT/bench1.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench1.json')); print('bench', '%.4g'%d['value'], '%.3f us'%(d['ms_per_step']*1e3), 'f64 %.3f us'%(d['f64']['ms_per_step']*1e3))"
 grep stamps $OUT/bench1.err
 timeout -k 10 120 python -u tools/probe_cold.py --out $OUT/cold_prod.json > $OUT/cold_prod.log 2> $OUT/cold_prod.err || { echo "probe2 failed"; tail -20 $OUT/cold_prod.err; exit 1; }

@@ -13,9 +13,9 @@ for w in lava65536 doorkey65536; do
   timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu --no-hbm --no-f64 > $OUT/direct_$w.json 2> $OUT/direct_$w.err || { echo "direct $w failed"; tail $OUT/direct_$w.err; exit 1; }
   summ $OUT/direct_$w.json direct_$w
   timeout -k 10 300 env MGDP_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29000 + RANDOM % 1000)) \
-    bench.py --workload $w --steps 20 --warmup 3 --no-cpu --no-hbm > $OUT/nccl1_$w.json 2> $OUT/nccl1_$w.err || { echo "nccl1 $w failed"; tail $OUT/nccl1_$w.err; exit 1; }
+    bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu --no-hbm > $OUT/nccl1_$w.json 2> $OUT/nccl1_$w.err || { echo "nccl1 $w failed"; tail $OUT/nccl1_$w.err; exit 1; }
   summ $OUT/nccl1_$w.json nccl1_$w
 done
 export MGDP_BENCH_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29000 + RANDOM % 1000))
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --workload lava65536 --steps 20 --warmup 3 --no-cpu --no-hbm > $OUT/prof_lava65536.json 2> $OUT/prof_lava65536.err || { echo "rocprof failed"; tail $OUT/prof_lava65536.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --workload lava65536 --steps 20 --warmup 3 --no-cpu --no-hbm > $OUT/prof_lava65536.json 2> $OUT/prof_lava65536.err || { echo "rocprof failed"; tail $OUT/prof_lava65536.err; exit 1; }
 echo "all ok"

@@ -12,7 +12,7 @@ fi
 for rep in $(seq 1 ${REPS:-3}); do
   for spec in ${KNOBS:-pair1=MGDP_SERVE_PAIR=1 pair0=MGDP_SERVE_PAIR=0}; do
     name=${spec%%=*}; envs=${spec#*=}
-    timeout -k 10 120 env ${envs//,/ } python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu --no-hbm --no-f64 ${BENCH_ARGS} > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err || { tail $OUT/bench_${name}_$rep.err; exit 1; }
+    timeout -k 10 120 env ${envs//,/ } python3 bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu --no-hbm --no-f64 ${BENCH_ARGS} > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err || { tail $OUT/bench_${name}_$rep.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$OUT/bench_${name}_$rep.json').read().strip().splitlines()[-1]); print('$name', d['value'], round(d['ms_per_step']*1e3, 3), 'us', d.get('lat_us'))"
   done
 done

@@ -12,10 +12,10 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 $OUT/smoke.log
 fi
 for i in 1 2; do
-  timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail $OUT/bench_$i.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail $OUT/bench_$i.err; exit 1; }
   tail -c 2500 $OUT/bench_$i.json
   echo
 done
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/rocprof -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu > $OUT/rocprof_bench.json 2> $OUT/rocprof_bench.err || { tail $OUT/rocprof_bench.err; exit 1; }
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 200 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench200.json 2> $OUT/bench200.err || { tail $OUT/bench200.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/rocprof -o run --output-format csv -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu > $OUT/rocprof_bench.json 2> $OUT/rocprof_bench.err || { tail $OUT/rocprof_bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 200 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench200.json 2> $OUT/bench200.err || { tail $OUT/bench200.err; exit 1; }
 tail -c 600 $OUT/bench200.json

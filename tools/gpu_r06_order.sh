@@ -29,6 +29,6 @@ for l in open('$OUT/ab.jsonl'):
 " | tee $OUT/summary.txt
 fi
 for o in ${ORDERS:-cells learned off}; do
-  timeout -k 10 300 env MGDP_ORDER=$o python3 bench.py --steps 20 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench_$o.json 2> $OUT/bench_$o.err || { tail $OUT/bench_$o.err; exit 1; }
+  timeout -k 10 300 env MGDP_ORDER=$o python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench_$o.json 2> $OUT/bench_$o.err || { tail $OUT/bench_$o.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/bench_$o.json').read().strip().splitlines()[-1]); print('$o', json.dumps(d['configs']))"
 done

@@ -19,7 +19,7 @@ done
 cat $OUT/serve.json
 for rep in 1 2; do
   for pair in 1 0; do
-    timeout -k 10 120 env MGDP_SERVE_PAIR=$pair python3 bench.py --steps 200 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench_p${pair}_$rep.json 2> $OUT/bench_p${pair}_$rep.err || { tail $OUT/bench_p${pair}_$rep.err; exit 1; }
+    timeout -k 10 120 env MGDP_SERVE_PAIR=$pair python3 bench.py --full --steps 200 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/bench_p${pair}_$rep.json 2> $OUT/bench_p${pair}_$rep.err || { tail $OUT/bench_p${pair}_$rep.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$OUT/bench_p${pair}_$rep.json').read().strip().splitlines()[-1]); print('pair=$pair', d['value'], round(d['ms_per_step']*1e3, 3), 'us', d.get('lat_us'))"
   done
 done

@@ -22,10 +22,10 @@ for dma in 1 0; do
 done
 PYTHONPATH=. timeout -k 10 120 python tools/probe_solve_py.py > $OUT/py_solve.json 2> $OUT/py_solve.err || { echo "py probe failed"; exit 1; }
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-hbm --no-sharded > $OUT/b$i.json 2> $OUT/b$i.err || { echo "bench failed"; tail $OUT/b$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-hbm --no-sharded > $OUT/b$i.json 2> $OUT/b$i.err || { echo "bench failed"; tail $OUT/b$i.err; exit 1; }
 done
 timeout -k 10 300 python bench.py --gpus 1 --steps 200 --warmup 5 --no-cpu --no-hbm --no-sharded --no-f64 > $OUT/b200.json 2> $OUT/b200.err || exit 1
-timeout -k 10 300 env MGDP_SERVE_EW=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-hbm --no-sharded > $OUT/b_ew0.json 2> $OUT/b_ew0.err || exit 1
+timeout -k 10 300 env MGDP_SERVE_EW=0 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-hbm --no-sharded > $OUT/b_ew0.json 2> $OUT/b_ew0.err || exit 1
 grep '"max_sweeps": 10000' $OUT/serve.json
 for f in $OUT/b*.json; do python -c "import json,sys; d=json.loads(open('$f').read().strip().splitlines()[-1]); print('$f', '%.4g'%d['value'], '%.3f us'%(d['ms_per_step']*1e3))"; done
 

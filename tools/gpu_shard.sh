@@ -15,7 +15,7 @@ for w in lava65536 doorkey65536; do
   timeout -k 10 300 env MGDP_BENCH_SHARD_OF=$n python bench.py --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/direct_${w}_of$n.json 2> $OUT/direct_${w}_of$n.err || { echo "direct $w of $n failed"; tail $OUT/direct_${w}_of$n.err; exit 1; }
   summ $OUT/direct_${w}_of$n.json direct_${w}_of$n
   timeout -k 10 300 env MGDP_BENCH_SHARD_OF=$n MGDP_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29000 + RANDOM % 1000)) \
-    bench.py --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/nccl1_${w}_of$n.json 2> $OUT/nccl1_${w}_of$n.err || { echo "nccl1 $w of $n failed"; tail $OUT/nccl1_${w}_of$n.err; exit 1; }
+    bench.py --full --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/nccl1_${w}_of$n.json 2> $OUT/nccl1_${w}_of$n.err || { echo "nccl1 $w of $n failed"; tail $OUT/nccl1_${w}_of$n.err; exit 1; }
   summ $OUT/nccl1_${w}_of$n.json nccl1_${w}_of$n
 done
 done

@@ -12,10 +12,10 @@ for w in ${WORKLOADS:-lava65536 doorkey65536}; do
   timeout -k 10 300 env MGDP_BENCH_SHARD_OF=8 MGDP_BENCH_SPLIT_EVENTS=1 python bench.py --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm --no-f64 > $OUT/direct_$w.json 2> $OUT/direct_$w.err || { echo "direct $w failed"; tail $OUT/direct_$w.err; exit 1; }
   summ $OUT/direct_$w.json direct_$w
   export MGDP_BENCH_SHARD_OF=8 MGDP_BENCH_FORCE_DIST=1 MGDP_BENCH_SPLIT_EVENTS=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29000 + RANDOM % 1000))
-  timeout -k 10 300 python bench.py --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/nccl1_$w.json 2> $OUT/nccl1_$w.err || { echo "nccl1 $w failed"; tail $OUT/nccl1_$w.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/nccl1_$w.json 2> $OUT/nccl1_$w.err || { echo "nccl1 $w failed"; tail $OUT/nccl1_$w.err; exit 1; }
   summ $OUT/nccl1_$w.json nccl1_$w
   export MASTER_PORT=$((29000 + RANDOM % 1000))
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$w -o run --output-format csv -- python3 bench.py --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/prof_$w.json 2> $OUT/prof_$w.err || { echo "rocprof $w failed"; tail $OUT/prof_$w.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$w -o run --output-format csv -- python3 bench.py --full --workload $w --steps 40 --warmup 5 --no-cpu --no-hbm > $OUT/prof_$w.json 2> $OUT/prof_$w.err || { echo "rocprof $w failed"; tail $OUT/prof_$w.err; exit 1; }
   summ $OUT/prof_$w.json prof_$w
   unset MGDP_BENCH_SHARD_OF MGDP_BENCH_FORCE_DIST MGDP_BENCH_SPLIT_EVENTS WORLD_SIZE RANK LOCAL_RANK MASTER_ADDR MASTER_PORT
 done

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-pmc}
 mkdir -p $OUT
 prof() { name=$1; ctr=$2; shift 2
-  timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace -T -d $OUT/${name}_${ctr} -o run --output-format csv -- python3 bench.py "$@" --no-cpu > $OUT/${name}_${ctr}.log 2>&1 || { echo "$name $ctr failed"; exit 1; }; }
+  timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace -T -d $OUT/${name}_${ctr} -o run --output-format csv -- python3 bench.py --full "$@" --no-cpu > $OUT/${name}_${ctr}.log 2>&1 || { echo "$name $ctr failed"; exit 1; }; }
 for c in FETCH_SIZE WRITE_SIZE; do
   prof step_doorkey16x65536 $c --workload step_doorkey16x65536 --steps 5 --warmup 1
   prof step_fourrooms65536 $c --workload step_fourrooms65536 --steps 5 --warmup 1
