@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/mgdp.h"
+#include "vi_layout.h"
 
 namespace mgdp {
 
@@ -65,7 +66,5 @@ struct DeviceGuard {
         active = outer;
     }
 };
-
-__host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 }  // namespace mgdp

@@ -24,7 +24,8 @@
 //   vi_sweep_kernel   one Jacobi sweep of every grid: per grid, V'[grid] is staged HBM->LDS (the
 //                     LDS tile of the neighbourhood), updated from LDS, written back.
 // Device code is split into vi_model.h (model), vi_loops.h (workgroup loops), vi_kernels.h
-// (kernels); this file holds the host side and the C ABI.
+// (kernels); this file holds the host side and the C ABI.  Which loop a handle runs is decided once,
+// in vi_plan.h (host-plain: plan_vi); vi_layout.h holds the LDS sizes host and device share.
 // Thread mappings (template MAP): MGDP_MAP_CELL = one thread per cell updating its 4 (XYD) or
 // 16 (DoorKey) states from 16-B LDS vectors; MGDP_MAP_SA = one thread per (state, action),
 // 8 lanes per state, wave shuffle max-reduce with the lowest action index winning ties.
@@ -38,12 +39,14 @@
 #include <climits>
 #include <limits>
 #include <type_traits>
+#include <utility>
 #include <cstring>
 #include <vector>
 
 #include "common.h"
 #include "comm.h"
 
+#include "vi_plan.h"
 #include "vi_model.h"
 #include "vi_loops.h"
 #include "vi_kernels.h"
@@ -54,10 +57,16 @@
 // ================================================================================================
 using namespace mgdp;
 
+// The kernels a plan names (resolve_kernels), type-erased: the fused own-rule and run-to launches
+// (they differ for Loop::dk_rows16 only), the lone-grid server, the batch server resident / past
+// its capacity (null unless the plan wants one).
+struct ViKernels {
+    const void *own = nullptr, *to = nullptr, *serve = nullptr, *bserve = nullptr, *bserve_multi = nullptr;
+};
+
 struct mgdp_vi {
     mgdp_vi_desc d;
     int S = 0, HW = 0, HWp = 0, A = 0, tsize = 0;
-    int HWs = 0, Ss = 0;  // see Geo
     hipStream_t stream = nullptr;
     bool own_stream = false;
     uint8_t *d_cells = nullptr;
@@ -65,24 +74,15 @@ struct mgdp_vi {
     int8_t *d_pi = nullptr;
     int32_t *d_kenv = nullptr;
     int32_t *d_kexec = nullptr;  // per grid: the sweep it last computed (fixed-point grids keep theirs)
-    // learned dispatch (Geo::order / kprio): set up from d_kexec at the first solve of cells that were
-    // already solved once (MGDP_LEARN_ORDER=0 turns the order off, MGDP_LEARN_PRIO=1 the priority on)
-    int32_t *d_order = nullptr;
+    int32_t *d_order = nullptr;  // dispatch order (Geo::order / kprio), from the cells at load or the last solve's d_kexec
     bool order_valid = false;
     int solves_since_load = 0;
     int kprio[3] = {0, 0, 0};
-    // measured (profiles/r05_ab2/): the order alone +3-6 % (LavaS11N5 x 8192 / x 65536, FourRooms x
-    // 4096, DoorKey-16 x 65536); the priority on top of it nothing or worse -- off by default
-    bool learn_order = true, learn_prio = false;
-    int order_src = 1;  // dispatch order key: 1 the cells' depth proxy (at load), 2 the last solve's sweeps, 0 none (MGDP_ORDER)
     double *d_dvenv = nullptr;
     unsigned long long *d_shards = nullptr;
     unsigned long long *d_red = nullptr;    // fused reduction shards [64][4]
     unsigned long long *d_pub1 = nullptr;   // device copy of a run_local launch's {kmax, dV, kmin, 0} (chained solve)
-    bool chain = true;                      // batched fused solve: run_local -> run_to(K from device memory), one host wait (MGDP_CHAIN=0: two)
-    int inkernel_max = kInKernelReduceMaxB; // batches up to this fold {k, dV} in the fused launch itself (MGDP_INKERNEL_MAX)
     unsigned int *d_ticket = nullptr;       // arrival ticket of the fused reduction
-    bool reduce_multi = true;               // B > inkernel_max: vi_reduce_multi_kernel (MGDP_REDUCE_MULTI)
     // host-mapped words (kHoutWords): [0..3] {kmax, dV hi, dV lo, kmin} of a launch (each tagged with
     // its epoch), [5..7] the server's tagged result, [8..9] trace stamps, [11] server exit word,
     // [12..13] the run_to mirror (tagged),
@@ -103,46 +103,22 @@ struct mgdp_vi {
     std::vector<int> ev_sweep;  // sweep index of each timed sweep launch (-1 = fused launch)
     double total_ms = 0.0;
     int64_t launches = 0;
-    int fused_block = 256;
-    int sweep_grid = 2048;
     int fresh = 1;          // next fused launch starts from V_0 = 0
     unsigned int epoch = 0; // tag of the last fused launch; its result lands in h_out[0..3]
-    int nbuf = 2;                 // fused LDS V buffers (3 = two-sweep XYD step)
-    int quad = 0;                 // fused XYD: 4 threads per cell
-    int pair = 0;                 // fused XYD: two-sweep step
-    int wave_p = 0;               // lone XYD grid on one wave: cells per lane (fused_wave_xyd)
-    int cpt = 1;                  // batched XYD fused path: cells per thread (MGDP_CPT; 2 = fused_fast_xyd_soa_x2)
-    int serve_ew = 0;             // served lone deterministic XYD grid on fused_serve_xyd (MGDP_SERVE_EW=0: off)
-    int serve_pair = 0;           // ... two sweeps per barrier, fused_serve_pair (MGDP_SERVE_PAIR=0: off)
-    int dk1t = 0;                 // batched fp32 DoorKey on one LDS tile (MGDP_DK_1T; fused_fast_dk_1t)
-    int dkhalf = 0;               // batched DoorKey, states split by has_key over two threads (MGDP_DK_HALF; fused_dk_half)
-    int dkrow = 0;                // batched DoorKey of width 16 on whole-row thread maps (MGDP_DK_ROWS; fused_dk_rows)
-    int pair2 = 1;                // batched plain XYD with cpt 2: adjacent-cell pairs (MGDP_PAIR2=0: fused_fast_xyd_soa_xn)
-    int wave2 = 0;                // batched plain XYD on one wave per grid: cells per lane P (fused_wave2_xyd; 0 = off)
-    int wave2n = 0;               // ... on two waves per grid instead: blocks per wave PW (fused_wave2n_xyd; 0 = off)
-    // ... mixed: two waves for the learned order's long grids, one for the rest (kWpMix; MGDP_MIX=1,
-    // fp32, P = wave2 in 2..6); nmix = the long grids (kexec >= mix_frac x the longest), set with the order
-    bool mix = false;
-    int nmix = 0;
-    double mix_frac = 0.75;
-    int band = 0;                 // ... on column bands of this many rows instead (fused_band_xyd; MGDP_BAND)
-    int sweep_block = 256;
-    int sweep_m = 1;              // grids staged per workgroup iteration (measured: m>1 no faster)
-    int sweep_pipe = 2;           // register-pipelined sweep kernel: grids fetched ahead (0 = staged kernel)
-    int pipe_grid = 0;            // its grid: resident workgroups (set at the first launch)
-    // SURVEY 8(f) item-3 options (NoDeath lava, finite horizon): vi_fused_opts_kernel
-    bool opts = false;
+    // what runs (vi_plan.h): the MGDP_* knobs, the plan made of them at create, the plan's kernels
+    ViKnobs kn;
+    ViPlan plan;
+    ViKernels k;
+    int nmix = 0;                 // Loop::mix: the long grids (kexec >= mix_frac x the longest), set with the order
+    int pipe_grid = 0;            // the pipelined sweep's grid: resident workgroups (set at the first launch)
     void *d_rgoal = nullptr;      // T[H]: the exact _reward() of step_count t+1, per t
     int8_t *d_pi_t = nullptr;     // int8[H][B][S] with MGDP_KEEP_POLICY_T
     // persistent solver (lone grid, fused one-thread-per-cell path): see vi_serve_kernel
-    bool persistent = true;       // MGDP_PERSISTENT=0 disables it
     bool serving = false;         // a vi_serve_kernel launch may be resident on `stream`
     // The server leaves after serve_idle_ticks without a request, which also bounds how long a
     // device-wide synchronisation by another component can wait on it.
     unsigned long long serve_idle_ticks = 10000;     // 100 us at 100 MHz
     unsigned long long serve_life_ticks = 200000000; // 2 s
-    int serve_pollers = 1;  // waves polling the request word (MGDP_SERVE_POLLERS; 1 measured 0.2-0.4 us faster than 4)
-    int serve_poll_dma = 1; // the server's polls land in an LDS mailbox, several in flight (MGDP_SERVE_POLL_DMA=0: one at a time)
     std::chrono::steady_clock::time_point serve_last{};  // host time of the last served result
     // A new lone grid for a resident server: the bytes wait at pending_src (host-mapped staging
     // h_stage, or the caller's device memory) and the next request carries kServeNewCells; a server
@@ -158,22 +134,9 @@ struct mgdp_vi {
     unsigned long long clk_tag = 0;  // the last server launch whose clock words were added
     double clk_cycles = 0.0, clk_ticks = 0.0, clk_busy = 0.0, clk_solves = 0.0;
     long long clk_launches = 0;
-    // the in-launch reduction (GkCtx, the wave2 family): one launch per batched deterministic solve
-    // (MGDP_GK=0 turns it off)
-    bool gk = false;
-    int gk_capacity = 0;          // resident workgroups of the wave2 kernel on this device (MGDP_GK=2)
-    unsigned long long *d_gk = nullptr;
-    // the resident batch server (vi_bserve_kernel): one-wave batches within its resident capacity,
-    // solves with launch timing off (MGDP_BSERVE=0: off)
-    bool bserve = true;
-    bool bserve_any = false;             // also batches past its resident capacity, several grids per workgroup (MGDP_BSERVE=2)
-    int bserve_cap = 0;                  // resident workgroups of vi_bserve_kernel on this device
-    int bserve_copies = kBreqCopies;     // request lines the workgroups poll (MGDP_BSERVE_COPIES)
-    int bserve_nap = 1;                  // s_sleep(10)s between polls (MGDP_BSERVE_NAP)
-    int bserve_wait_pub = 1;             // the forwarder polls the host only after the publication (MGDP_BSERVE_WAIT_PUB)
+    unsigned long long *d_gk = nullptr;    // the in-launch reduction's device words (GkCtx; plan.gk)
+    unsigned long long *d_breq = nullptr;  // the resident batch server's device words (kBreqWords): forwarded request, exit counter
     bool solving = false;                // inside mgdp_vi_solve: its run_local may use the batch server
-    double bserve_prio_frac = 0.0;       // this fraction of the dispatch order's longest grids sweeps at a higher issue priority (MGDP_BSERVE_PRIO_FRAC)
-    unsigned long long *d_breq = nullptr;  // its device words (kBreqWords): forwarded request, exit counter
 };
 
 namespace {
@@ -185,23 +148,23 @@ Geo make_geo(const mgdp_vi *vi) {
     g.H = vi->d.H;
     g.HW = vi->HW;
     g.HWp = vi->HWp;
-    g.HWs = vi->HWs;
-    g.Ss = vi->Ss;
+    g.HWs = vi->plan.HWs;
+    g.Ss = vi->plan.Ss;
     g.S = vi->S;
     g.off[0] = 1;
     g.off[1] = vi->d.W;
     g.off[2] = -1;
     g.off[3] = -vi->d.W;
     g.max_sweeps = vi->d.max_sweeps;
-    g.nbuf = vi->nbuf;
-    g.quad = vi->quad;
-    g.pair = vi->pair;
+    g.nbuf = vi->plan.nbuf;
+    g.quad = vi->plan.quad;
+    g.pair = vi->plan.pair;
     g.tol = vi->d.tol;
     g.kexec = vi->d_kexec;
-    g.order = vi->order_valid && vi->learn_order ? vi->d_order : nullptr;
-    for (int i = 0; i < 3; ++i) g.kprio[i] = vi->order_valid && vi->learn_prio ? vi->kprio[i] : 0;
-    g.nmix = g.order && vi->mix ? vi->nmix : 0;
-    g.wt = vi->gk_capacity > 0 && vi->d.B <= vi->gk_capacity;
+    g.order = vi->order_valid && vi->kn.learn_order ? vi->d_order : nullptr;
+    for (int i = 0; i < 3; ++i) g.kprio[i] = vi->order_valid && vi->kn.learn_prio ? vi->kprio[i] : 0;
+    g.nmix = g.order && (vi->plan.kern == Loop::mix) ? vi->nmix : 0;
+    g.wt = vi->plan.wt;
     return g;
 }
 
@@ -267,7 +230,7 @@ inline unsigned int next_host_epoch(mgdp_vi *vi) {
 }
 
 inline void launch_reduce(mgdp_vi *vi, unsigned long long *pub) {
-    if (vi->reduce_multi)
+    if (vi->kn.reduce_multi)
         hipLaunchKernelGGL(vi_reduce_multi_kernel, dim3(kRedShards), dim3(256), 0, vi->stream, vi->d_kenv, vi->d_dvenv,
                            vi->d.B, vi->d_red, vi->d_ticket, pub, pub == vi->d_hout ? vi->epoch : 0u);
     else
@@ -278,18 +241,18 @@ inline void launch_reduce(mgdp_vi *vi, unsigned long long *pub) {
 template <typename T, int MODEL, bool SLIP, bool ND, int HMODE>
 int launch_opts_t(mgdp_vi *vi, int k_target) {
     const Geo g = make_geo(vi);
-    const Smem L = smem_layout(vi->Ss, vi->HWp, sizeof(T), vi->nbuf);
+    const Smem L = smem_layout(vi->plan.Ss, vi->HWp, sizeof(T), vi->plan.nbuf);
     auto kern = vi_fused_opts_kernel<T, MODEL, SLIP, ND, HMODE>;
     if (L.total() > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total()));
     TimedPair tp;
     if (int rc = timed_begin(vi, -1, &tp)) return rc;
-    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(vi->fused_block), L.total(), vi->stream, tp.a, tp.b, 0, g,
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(vi->plan.block), L.total(), vi->stream, tp.a, tp.b, 0, g,
                           make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv,
                           vi->d_red, vi->d_ticket, vi->d_hout, k_target, vi->fresh,
-                          vi->d.B <= vi->inkernel_max ? 1 : 0, next_host_epoch(vi), (const T *)vi->d_rgoal, vi->d_pi_t);
+                          vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi), (const T *)vi->d_rgoal, vi->d_pi_t);
     MGDP_HIP(hipGetLastError());
     vi->fresh = 0;
-    if (vi->d.B > vi->inkernel_max) {
+    if (vi->d.B > vi->kn.inkernel_max) {
         launch_reduce(vi, vi->d_hout);
         MGDP_HIP(hipGetLastError());
     }
@@ -314,169 +277,104 @@ int launch_opts(mgdp_vi *vi, int k_target) {
               : launch_opts_h<T, MGDP_MODEL_XYD, false, false>(vi, k_target);
 }
 
-// Kernel variant: the one-wave lone-grid instantiation when vi->wave_p is set (XYD, cell mapping).
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP>
-auto pick_wave(const mgdp_vi *vi) -> decltype(K<T, MODEL, SLIP, MAP, 0>::fn) {
+// K<L, n>::fn for the run-time n among NS...; `dflt` if n is none of them.  The sequences below are
+// exactly the sizes each family is compiled for.
+template <template <Loop, int> class K, Loop L, typename F, int... NS>
+F pick(int n, F dflt, std::integer_sequence<int, NS...>) {
+    ((n == NS ? (void)(dflt = K<L, NS>::fn) : (void)0), ...);
+    return dflt;
+}
+using N1to8 = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;  // wave2, band, dk_half and pair2 strides, bserve
+using NWave = std::integer_sequence<int, 1, 2, 4, 8>;              // lone wave: cells per lane
+using NMix = std::integer_sequence<int, 2, 3, 4, 5, 6>;            // mix (fp32)
+using NWave2n = std::integer_sequence<int, 2, 3, 4>;               // wave2n: blocks per wave
+
+template <typename T, int MODEL, bool SLIP, int MAP>
+struct Kernels {
+    template <Loop L, int N> struct Fused { static constexpr auto fn = vi_fused_kernel<T, MODEL, SLIP, MAP, L, N>; };
+    template <Loop L, int N> struct Serve { static constexpr auto fn = vi_serve_kernel<T, MODEL, SLIP, MAP, L, N>; };
+    template <Loop, int P> struct BServe { static constexpr auto fn = vi_bserve_kernel<T, P, false>; };
+    template <Loop, int P> struct BServeMulti { static constexpr auto fn = vi_bserve_kernel<T, P, true>; };
+};
+// A kernel's signature depends on the value type alone: a launch casts the handle's pointer back.
+template <typename T> using FusedFn = decltype(&vi_fused_kernel<T, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>);
+template <typename T> using ServeFn = decltype(&vi_serve_kernel<T, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>);
+template <typename T> using BServeFn = decltype(&vi_bserve_kernel<T, 1, false>);
+
+// The plan's kernels.  A plan that names an instantiation this (dtype, model, slip, mapping) does not
+// hold is an error, never another kernel.
+template <typename T, int MODEL, bool SLIP, int MAP>
+int resolve_kernels(const ViPlan &p, ViKernels *out) {
+    using KS = Kernels<T, MODEL, SLIP, MAP>;
+    FusedFn<T> f = KS::template Fused<Loop::generic, 0>::fn, own = nullptr;
+    ServeFn<T> s = KS::template Serve<Loop::generic, 0>::fn;
+    BServeFn<T> b = nullptr, bm = nullptr;
+    bool f_ok = p.kern == Loop::generic, s_ok = p.serve_kern == Loop::generic;
+    auto fused = [&](FusedFn<T> k) { f_ok = f_ok || k != f; f = k; };
+    auto serve = [&](ServeFn<T> k) { s_ok = s_ok || k != s; s = k; };
+    if constexpr (MAP == MGDP_MAP_CELL) {
+        constexpr Loop soa = MODEL == MGDP_MODEL_XYD ? Loop::xyd_soa : Loop::dk_soa;
+        if (p.kern == soa) fused(KS::template Fused<soa, 0>::fn);
+    }
     if constexpr (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL) {
-        switch (vi->wave_p) {
-        case 1: return K<T, MODEL, SLIP, MAP, 1>::fn;
-        case 2: return K<T, MODEL, SLIP, MAP, 2>::fn;
-        case 4: return K<T, MODEL, SLIP, MAP, 4>::fn;
-        case 8: return K<T, MODEL, SLIP, MAP, 8>::fn;
-        default: break;
+        if (p.kern == Loop::wave) fused(pick<KS::template Fused, Loop::wave>(p.n, f, NWave{}));
+        if (p.kern == Loop::xyd_x2) fused(KS::template Fused<Loop::xyd_x2, 0>::fn);
+        if (p.kern == Loop::xyd_x4) fused(KS::template Fused<Loop::xyd_x4, 0>::fn);
+        if (p.serve_kern == Loop::wave) serve(pick<KS::template Serve, Loop::wave>(p.serve_n, s, NWave{}));
+        if (p.serve_kern == Loop::xyd_x2) serve(KS::template Serve<Loop::xyd_x2, 0>::fn);
+        if constexpr (!SLIP) {
+            if (p.kern == Loop::xyd_pair2) fused(pick<KS::template Fused, Loop::xyd_pair2>(p.n, f, N1to8{}));
+            if (p.kern == Loop::wave2) fused(pick<KS::template Fused, Loop::wave2>(p.n, f, N1to8{}));
+            if (p.kern == Loop::band) fused(pick<KS::template Fused, Loop::band>(p.n, f, N1to8{}));
+            if (p.kern == Loop::wave2n) fused(pick<KS::template Fused, Loop::wave2n>(p.n, f, NWave2n{}));
+            if constexpr (std::is_same<T, float>::value)
+                if (p.kern == Loop::mix) fused(pick<KS::template Fused, Loop::mix>(p.n, f, NMix{}));
+            if (p.serve_kern == Loop::serve_ew) serve(KS::template Serve<Loop::serve_ew, 0>::fn);
+            if (p.serve_kern == Loop::serve_pair) serve(KS::template Serve<Loop::serve_pair, 0>::fn);
+            if (p.serve_kern == Loop::band) serve(pick<KS::template Serve, Loop::band>(p.serve_n, s, N1to8{}));
+            if (p.wants_bserve) {  // the wave2 loop of the same P (the capacity of both is the same by bserve_min_waves)
+                b = pick<KS::template BServe, Loop::wave2>(p.wave2, b, N1to8{});
+                bm = pick<KS::template BServeMulti, Loop::wave2>(p.wave2, bm, N1to8{});
+            }
         }
     }
-    return K<T, MODEL, SLIP, MAP, 0>::fn;
-}
-template <typename T, int MODEL, bool SLIP, int MAP, int WP>
-struct FusedK { static constexpr auto fn = vi_fused_kernel<T, MODEL, SLIP, MAP, WP>; };
-// The one-wave-per-grid instantiation for P cells per lane (1..8); `dflt` if P is out of range.
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP, typename F>
-F pick_wave2(int P, F dflt) {
-    constexpr int PMAX = 8;
-    switch (P) {
-    case 1: return K<T, MODEL, SLIP, MAP, kWpWave2 - 1>::fn;
-    case 2: return K<T, MODEL, SLIP, MAP, kWpWave2 - 2>::fn;
-    case 3: return K<T, MODEL, SLIP, MAP, kWpWave2 - 3>::fn;
-    case 4: return K<T, MODEL, SLIP, MAP, kWpWave2 - 4>::fn;
-    default: break;
-    }
-    if constexpr (PMAX > 4) {
-        switch (P) {
-        case 5: return K<T, MODEL, SLIP, MAP, kWpWave2 - 5>::fn;
-        case 6: return K<T, MODEL, SLIP, MAP, kWpWave2 - 6>::fn;
-        case 7: return K<T, MODEL, SLIP, MAP, kWpWave2 - 7>::fn;
-        case 8: return K<T, MODEL, SLIP, MAP, kWpWave2 - 8>::fn;
-        default: break;
+    if constexpr (MODEL == MGDP_MODEL_DOORKEY && MAP == MGDP_MAP_CELL && !SLIP) {
+        if (p.kern == Loop::dk_1t) fused(KS::template Fused<Loop::dk_1t, 0>::fn);
+        if (p.kern == Loop::dk_half) fused(pick<KS::template Fused, Loop::dk_half>(p.n, f, N1to8{}));
+        if (p.kern == Loop::dk_rows) {
+            fused(KS::template Fused<Loop::dk_rows, 0>::fn);
+            // fp32 16x16 own-rule launches: the compile-time 256-thread variant
+            if (sizeof(T) == 4 && p.HWs == 256 && p.block == 256) own = KS::template Fused<Loop::dk_rows16, 0>::fn;
         }
+        if (p.serve_kern == Loop::dk_half) serve(pick<KS::template Serve, Loop::dk_half>(p.serve_n, s, N1to8{}));
     }
-    return dflt;
-}
-// The column-band instantiation for HB rows per band (1..8); `dflt` if out of range.
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP, typename F>
-F pick_band(int HB, F dflt) {
-    switch (HB) {
-    case 1: return K<T, MODEL, SLIP, MAP, kWpBand - 1>::fn;
-    case 2: return K<T, MODEL, SLIP, MAP, kWpBand - 2>::fn;
-    case 3: return K<T, MODEL, SLIP, MAP, kWpBand - 3>::fn;
-    case 4: return K<T, MODEL, SLIP, MAP, kWpBand - 4>::fn;
-    case 5: return K<T, MODEL, SLIP, MAP, kWpBand - 5>::fn;
-    case 6: return K<T, MODEL, SLIP, MAP, kWpBand - 6>::fn;
-    case 7: return K<T, MODEL, SLIP, MAP, kWpBand - 7>::fn;
-    case 8: return K<T, MODEL, SLIP, MAP, kWpBand - 8>::fn;
-    default: return dflt;
-    }
-}
-// The mixed-wave-count instantiation for P blocks of 64 cells (2..6, fp32); `dflt` otherwise.
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP, typename F>
-F pick_mix(int P, F dflt) {
-    if constexpr (std::is_same<T, float>::value) {
-        switch (P) {
-        case 2: return K<T, MODEL, SLIP, MAP, kWpMix - 2>::fn;
-        case 3: return K<T, MODEL, SLIP, MAP, kWpMix - 3>::fn;
-        case 4: return K<T, MODEL, SLIP, MAP, kWpMix - 4>::fn;
-        case 5: return K<T, MODEL, SLIP, MAP, kWpMix - 5>::fn;
-        case 6: return K<T, MODEL, SLIP, MAP, kWpMix - 6>::fn;
-        default: break;
-        }
-    }
-    return dflt;
-}
-// The two-waves-per-grid instantiation for PW blocks per wave (2..4); `dflt` if out of range.
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP, typename F>
-F pick_wave2n(int PW, F dflt) {
-    switch (PW) {
-    case 2: return K<T, MODEL, SLIP, MAP, kWpWave2n - 2>::fn;
-    case 3: return K<T, MODEL, SLIP, MAP, kWpWave2n - 3>::fn;
-    case 4: return K<T, MODEL, SLIP, MAP, kWpWave2n - 4>::fn;
-    default: return dflt;
-    }
-}
-template <typename T, int MODEL, bool SLIP, int MAP, int WP>
-struct ServeK { static constexpr auto fn = vi_serve_kernel<T, MODEL, SLIP, MAP, WP>; };
-// fused_dk_half variants by plane stride HWs = 64 * n (the host allows n <= 8)
-template <template <typename, int, bool, int, int> class K, typename T, int MODEL, bool SLIP, int MAP, typename F>
-F pick_dkhalf(int n, F dflt) {
-    switch (n) {
-    case 1: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 1>::fn;
-    case 2: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 2>::fn;
-    case 3: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 3>::fn;
-    case 4: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 4>::fn;
-    case 5: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 5>::fn;
-    case 6: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 6>::fn;
-    case 7: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 7>::fn;
-    case 8: return K<T, MODEL, SLIP, MAP, kWpDkHalf - 8>::fn;
-    default: return dflt;
-    }
+    MGDP_CHECK(f_ok && s_ok && (!p.wants_bserve || (b && bm)), MGDP_E_INVALID,
+               "no kernel for the planned loop (%s size %d, served %s size %d)", name(p.kern, false), p.n,
+               name(p.serve_kern, true), p.serve_n);
+    out->to = (const void *)f;
+    out->own = own ? (const void *)own : (const void *)f;
+    out->serve = (const void *)s;
+    out->bserve = (const void *)b;
+    out->bserve_multi = (const void *)bm;
+    return 0;
 }
 
 // pub: where the launch's {kmax, dV bits, kmin} go (default: the host-mapped words the host polls,
 // epoch-tagged; the multi-GPU device protocol passes a device buffer it all-reduces, raw); k_dev: the target
 // sweep read from device memory instead of k_target (mgdp_vi_run_to_dev).
-template <typename T, int MODEL, bool SLIP, int MAP>
-int launch_fused_t(mgdp_vi *vi, int k_target, unsigned long long *pub = nullptr, const long long *k_dev = nullptr,
-                   unsigned long long *mirror = nullptr) {
-    if (vi->opts) return launch_opts<T>(vi, k_target);
+template <typename T>
+int launch_fused_t(mgdp_vi *vi, int k_target, unsigned long long *pub, const long long *k_dev, unsigned long long *mirror) {
+    if (vi->plan.opts) return launch_opts<T>(vi, k_target);
     if (!pub) pub = vi->d_hout;
     const Geo g = make_geo(vi);
-    const Smem L = smem_layout(vi->Ss, vi->HWp, sizeof(T), vi->nbuf);
-    auto kern = pick_wave<FusedK, T, MODEL, SLIP, MAP>(vi);
-    if constexpr (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL) {
-        if (vi->cpt == 2) kern = FusedK<T, MODEL, SLIP, MAP, -2>::fn;
-        else if (vi->cpt == 4) kern = FusedK<T, MODEL, SLIP, MAP, -4>::fn;
-        if constexpr (!SLIP) {  // two adjacent cells per thread, compile-time plane stride
-            if (vi->cpt == 2 && vi->pair2 && vi->HWs == 2 * vi->fused_block && vi->HWs % 128 == 0 && vi->HWs <= 1024) {
-                switch (vi->HWs / 128) {
-                case 1: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 1>::fn; break;
-                case 2: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 2>::fn; break;
-                case 3: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 3>::fn; break;
-                case 4: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 4>::fn; break;
-                case 5: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 5>::fn; break;
-                case 6: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 6>::fn; break;
-                case 7: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 7>::fn; break;
-                case 8: kern = FusedK<T, MODEL, SLIP, MAP, kWpPair - 8>::fn; break;
-                default: break;
-                }
-            }
-        }
-    }
-    if constexpr (MODEL == MGDP_MODEL_DOORKEY && MAP == MGDP_MAP_CELL && !SLIP) {
-        if (vi->dk1t) kern = FusedK<T, MODEL, SLIP, MAP, kWpDk1t>::fn;
-        else if (vi->dkhalf) kern = pick_dkhalf<FusedK, T, MODEL, SLIP, MAP>(vi->HWs / 64, kern);
-        else if (vi->dkrow)  // fp32 16x16 own-rule launches: the compile-time 256-thread variant
-            kern = (sizeof(T) == 4 && vi->HWs == 256 && vi->fused_block == 256 && k_target < 0 && !k_dev)
-                       ? FusedK<T, MODEL, SLIP, MAP, kWpDkRow16>::fn
-                       : FusedK<T, MODEL, SLIP, MAP, kWpDkRow>::fn;
-    }
-    if constexpr (MAP == MGDP_MAP_CELL) {  // one cell per thread, direction-major: the stripped variant
-        if (kern == FusedK<T, MODEL, SLIP, MAP, 0>::fn && !vi->pair && !vi->quad && vi->HW <= vi->fused_block)
-            kern = FusedK<T, MODEL, SLIP, MAP, kWpSoa>::fn;
-    }
-    int smem = L.total();
-    if constexpr (MODEL == MGDP_MODEL_DOORKEY && MAP == MGDP_MAP_CELL && !SLIP) {
-        if (vi->dkrow && !vi->dk1t && !vi->dkhalf) smem = dkrow_smem_bytes(vi->HWp, vi->HWs, (int)sizeof(T));
-    }
-    if constexpr (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL && !SLIP) {
-        if (vi->mix) {
-            kern = pick_mix<FusedK, T, MODEL, SLIP, MAP>(vi->wave2, kern);
-            smem = mix_smem_bytes(vi->HWp, vi->d.W, vi->wave2, (int)sizeof(T));
-        } else if (vi->wave2n) {
-            kern = pick_wave2n<FusedK, T, MODEL, SLIP, MAP>(vi->wave2n, kern);
-            smem = wave2n_smem_bytes(vi->HWp, vi->d.W, 2 * vi->wave2n, (int)sizeof(T));
-        } else if (vi->band) {
-            kern = pick_band<FusedK, T, MODEL, SLIP, MAP>(vi->band, kern);
-            smem = 256 + (vi->HWp + 15) / 16 * 16;
-        } else if (vi->wave2) {
-            kern = pick_wave2<FusedK, T, MODEL, SLIP, MAP>(vi->wave2, kern);
-            smem = wave2_smem_bytes(vi->HWp, vi->d.W, vi->wave2, (int)sizeof(T));
-        }
-    }
-    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    const bool own_rule = k_target < 0 && !k_dev;
+    const auto kern = reinterpret_cast<FusedFn<T>>(const_cast<void *>(own_rule ? vi->k.own : vi->k.to));
+    const int block = vi->plan.block, smem = vi->plan.lds;
     static const bool debug_occ = std::getenv("MGDP_DEBUG_OCC") != nullptr;  // read once, not per launch
     if (debug_occ) {  // diagnostics: resident workgroups per CU of this launch
         int per_cu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, vi->fused_block, smem);
-        std::fprintf(stderr, "mgdp occupancy: %d workgroups/CU (block %d, LDS %d B)\n", per_cu, vi->fused_block, smem);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, block, smem);
+        std::fprintf(stderr, "mgdp occupancy: %d workgroups/CU (block %d, LDS %d B)\n", per_cu, block, smem);
     }
     TimedPair tp;
     if (int rc = timed_begin(vi, -1, &tp)) return rc;
@@ -484,110 +382,72 @@ int launch_fused_t(mgdp_vi *vi, int k_target, unsigned long long *pub = nullptr,
     // each grid's {k_e, dV at k_e} through the counter tree and publishes {kmax, dV, kmin} itself (no
     // reduce kernel); grids at an exact fixed point are complete for any K (fixed-point completion),
     // so run_to has nothing to launch unless some grid stopped with dV > 0
-    unsigned long long *gk = (vi->gk && k_target < 0 && vi->fresh && !k_dev) ? vi->d_gk : nullptr;
-    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(vi->fused_block), smem, vi->stream, tp.a, tp.b, 0, g,
+    unsigned long long *gk = (vi->plan.gk && own_rule && vi->fresh) ? vi->d_gk : nullptr;
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(block), smem, vi->stream, tp.a, tp.b, 0, g,
                        make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv,
                        vi->d_dvenv, vi->d_red, vi->d_ticket, pub, k_target, vi->fresh,
-                       vi->d.B <= vi->inkernel_max ? 1 : 0, pub == vi->d_hout ? next_host_epoch(vi) : 0u, k_dev, mirror, gk);
+                       vi->d.B <= vi->kn.inkernel_max ? 1 : 0, pub == vi->d_hout ? next_host_epoch(vi) : 0u, k_dev, mirror, gk);
     MGDP_HIP(hipGetLastError());
     vi->fresh = 0;
-    if (vi->d.B > vi->inkernel_max && !gk) {  // a launch-wide-rule launch publishes its own reduction
+    if (vi->d.B > vi->kn.inkernel_max && !gk) {  // a launch-wide-rule launch publishes its own reduction
         launch_reduce(vi, pub);
         MGDP_HIP(hipGetLastError());
     }
     return 0;
 }
+int launch_fused(mgdp_vi *vi, int k_target, unsigned long long *pub = nullptr, const long long *k_dev = nullptr,
+                 unsigned long long *mirror = nullptr) {
+    return vi->d.dtype == MGDP_F32 ? launch_fused_t<float>(vi, k_target, pub, k_dev, mirror)
+                                   : launch_fused_t<double>(vi, k_target, pub, k_dev, mirror);
+}
 
 void account_server_clock(mgdp_vi *vi);
 
-// The batch server's instantiation for P cells per lane (the wave2 kernel's P); nullptr if out of range.
+// Launch the handle's server: the resident batch server (B > 1; bserve_eligible: a one-wave
+// deterministic XYD batch) or the lone-grid server.
 template <typename T>
-const void *pick_bserve(int P) {  // the resident instantiation (the capacity of both is the same by bserve_min_waves)
-    switch (P) {
-    case 1: return (const void *)vi_bserve_kernel<T, 1>;
-    case 2: return (const void *)vi_bserve_kernel<T, 2>;
-    case 3: return (const void *)vi_bserve_kernel<T, 3>;
-    case 4: return (const void *)vi_bserve_kernel<T, 4>;
-    case 5: return (const void *)vi_bserve_kernel<T, 5>;
-    case 6: return (const void *)vi_bserve_kernel<T, 6>;
-    case 7: return (const void *)vi_bserve_kernel<T, 7>;
-    case 8: return (const void *)vi_bserve_kernel<T, 8>;
-    default: return nullptr;
-    }
-}
-template <typename T, int P>
-int launch_bserve_p(mgdp_vi *vi, unsigned int served, TimedPair tp) {
-    const int smem = wave2_smem_bytes(vi->HWp, vi->d.W, P, (int)sizeof(T));
-    static const bool force_multi = std::getenv("MGDP_BSERVE_FORCE_MULTI") != nullptr;  // diagnostics
-    auto kern = (vi->d.B > vi->bserve_cap || force_multi) ? vi_bserve_kernel<T, P, true> : vi_bserve_kernel<T, P, false>;
-    hipExtLaunchKernelGGL(kern, dim3(std::min(vi->d.B, vi->bserve_cap)), dim3(64), smem, vi->stream, tp.a, tp.b, 0, make_geo(vi),
-                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv, vi->d_hout,
-                          vi->d_hout + kHoutReq, vi->d_breq, vi->d_gk, (unsigned long long)served, vi->serve_idle_ticks,
-                          vi->serve_life_ticks, vi->serve_tag, vi->bserve_copies, vi->bserve_nap, vi->bserve_wait_pub,
-                          vi->order_valid && vi->learn_order ? (int)(vi->bserve_prio_frac * vi->d.B) : 0);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-template <typename T, int MODEL, bool SLIP, int MAP>
 int launch_serve_t(mgdp_vi *vi, unsigned int served) {
-    if (vi->d.B > 1) {  // the resident batch server (bserve_eligible: deterministic XYD, one wave per grid)
-        if constexpr (MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL) {
-            TimedPair tp;
-            if (int rc = timed_begin(vi, -1, &tp)) return rc;
-            account_server_clock(vi);
-            ++vi->serve_tag;
-            switch (vi->wave2) {
-            case 1: return launch_bserve_p<T, 1>(vi, served, tp);
-            case 2: return launch_bserve_p<T, 2>(vi, served, tp);
-            case 3: return launch_bserve_p<T, 3>(vi, served, tp);
-            case 4: return launch_bserve_p<T, 4>(vi, served, tp);
-            case 5: return launch_bserve_p<T, 5>(vi, served, tp);
-            case 6: return launch_bserve_p<T, 6>(vi, served, tp);
-            case 7: return launch_bserve_p<T, 7>(vi, served, tp);
-            case 8: return launch_bserve_p<T, 8>(vi, served, tp);
-            default: break;
-            }
-        }
-        MGDP_CHECK(false, MGDP_E_INVALID, "batch server: not a one-wave deterministic XYD batch");
-    }
+    const ViPlan &p = vi->plan;
+    const bool batch = vi->d.B > 1;
+    MGDP_CHECK(!batch || vi->k.bserve, MGDP_E_INVALID, "batch server: not a one-wave deterministic XYD batch");
     const Geo g = make_geo(vi);
-    const Smem L = smem_layout(vi->Ss, vi->HWp, sizeof(T), vi->nbuf);
-    auto kern = pick_wave<ServeK, T, MODEL, SLIP, MAP>(vi);
-    int smem = L.total();
-    if constexpr (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL) {
-        if (vi->cpt == 2) kern = ServeK<T, MODEL, SLIP, MAP, -2>::fn;
-        if constexpr (!SLIP) {
-            if (vi->serve_ew) kern = vi->serve_pair ? ServeK<T, MODEL, SLIP, MAP, kWpServePair>::fn
-                                                    : ServeK<T, MODEL, SLIP, MAP, kWpServeEw>::fn;
-            if (vi->band) kern = pick_band<ServeK, T, MODEL, SLIP, MAP>(vi->band, kern);
-        }
-    }
-    if constexpr (MODEL == MGDP_MODEL_DOORKEY && MAP == MGDP_MAP_CELL && !SLIP) {
-        if (vi->dkhalf) kern = pick_dkhalf<ServeK, T, MODEL, SLIP, MAP>(vi->HWs / 64, kern);
-    }
-    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     TimedPair tp;
     if (int rc = timed_begin(vi, -1, &tp)) return rc;
     account_server_clock(vi);  // a server that left on its own (idle / life limit) before this relaunch
     ++vi->serve_tag;
-    hipExtLaunchKernelGGL(kern, dim3(1), dim3(vi->fused_block), smem, vi->stream, tp.a, tp.b, 0, g,
-                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv,
-                          vi->d_hout, vi->d_hout + kHoutReq, (unsigned long long)served, vi->serve_idle_ticks,
-                          vi->serve_life_ticks, vi->serve_pollers, vi->serve_tag, vi->serve_poll_dma);
+    if (batch) {
+        static const bool force_multi = std::getenv("MGDP_BSERVE_FORCE_MULTI") != nullptr;  // diagnostics
+        const bool multi = vi->d.B > p.bserve_cap || force_multi;
+        const auto kern = reinterpret_cast<BServeFn<T>>(const_cast<void *>(multi ? vi->k.bserve_multi : vi->k.bserve));
+        hipExtLaunchKernelGGL(kern, dim3(std::min(vi->d.B, p.bserve_cap)), dim3(64), p.lds, vi->stream, tp.a, tp.b, 0, g,
+                              make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv, vi->d_hout,
+                              vi->d_hout + kHoutReq, vi->d_breq, vi->d_gk, (unsigned long long)served, vi->serve_idle_ticks,
+                              vi->serve_life_ticks, vi->serve_tag, vi->kn.bserve_copies, vi->kn.bserve_nap,
+                              vi->kn.bserve_wait_pub,
+                              vi->order_valid && vi->kn.learn_order ? (int)(vi->kn.bserve_prio_frac * vi->d.B) : 0);
+    } else {
+        const auto kern = reinterpret_cast<ServeFn<T>>(const_cast<void *>(vi->k.serve));
+        hipExtLaunchKernelGGL(kern, dim3(1), dim3(p.block), p.serve_lds, vi->stream, tp.a, tp.b, 0, g,
+                              make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv,
+                              vi->d_hout, vi->d_hout + kHoutReq, (unsigned long long)served, vi->serve_idle_ticks,
+                              vi->serve_life_ticks, vi->kn.serve_pollers, vi->serve_tag, vi->kn.serve_poll_dma);
+    }
     MGDP_HIP(hipGetLastError());
     return 0;
+}
+int launch_serve(mgdp_vi *vi, unsigned int served) {
+    return vi->d.dtype == MGDP_F32 ? launch_serve_t<float>(vi, served) : launch_serve_t<double>(vi, served);
 }
 
 template <typename T, int MODEL, bool SLIP, int MAP, bool POLICY>
 int launch_sweep_kernel(mgdp_vi *vi, const T *Vin, T *Vout, int k, int check_prev, TimedPair tp = {}) {
-    const int m = vi->sweep_m;
+    const int m = vi->plan.sweep_m;
     const int smem = sweep_smem_bytes(vi->S, vi->HWp, sizeof(T), m);
     auto kern = vi_sweep_kernel<T, MODEL, SLIP, MAP, POLICY>;
     if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     const int groups = (vi->d.B + m - 1) / m;
-    const int grid = std::min(groups, vi->sweep_grid);
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(vi->sweep_block), smem, vi->stream, tp.a, tp.b, 0, make_geo(vi), make_coef<T>(vi),
+    const int grid = std::min(groups, vi->plan.sweep_grid);
+    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(vi->plan.sweep_block), smem, vi->stream, tp.a, tp.b, 0, make_geo(vi), make_coef<T>(vi),
                        vi->d_cells, Vin, Vout, vi->d_pi, POLICY ? nullptr : vi->d_shards, k, check_prev, m);
     MGDP_HIP(hipGetLastError());
     return 0;
@@ -595,7 +455,7 @@ int launch_sweep_kernel(mgdp_vi *vi, const T *Vin, T *Vout, int k, int check_pre
 
 template <typename T, int MODEL, bool SLIP, int DEPTH>
 int launch_sweep_pipe(mgdp_vi *vi, const T *Vin, T *Vout, int k, int check_prev, TimedPair tp) {
-    const int smem = sweep_pipe_smem_bytes(vi->S, vi->HW, vi->HWs, vi->HWp, sizeof(T));
+    const int smem = sweep_pipe_smem_bytes(vi->S, vi->HW, vi->plan.HWs, vi->HWp, sizeof(T));
     auto kern = vi_sweep_pipe_kernel<T, MODEL, SLIP, DEPTH>;
     if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     if (vi->pipe_grid == 0) {  // resident workgroups, at most 4 per CU
@@ -604,13 +464,13 @@ int launch_sweep_pipe(mgdp_vi *vi, const T *Vin, T *Vout, int k, int check_prev,
         // 2 109.3: four 256-thread workgroups, each with two grids' loads in flight, keep enough bytes
         // moving, and fewer co-resident workgroups contend less for the channels.
         int per_cu = 0, cus = 0;
-        MGDP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, vi->HWs, smem));
+        MGDP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, vi->plan.HWs, smem));
         MGDP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, vi->d.device));
         vi->pipe_grid = std::min(4, std::max(1, per_cu)) * std::max(1, cus);
-        if (const char *ev = std::getenv("MGDP_SWEEP_GRID")) vi->pipe_grid = std::max(1, std::atoi(ev));
+        if (vi->kn.sweep_grid > 0) vi->pipe_grid = vi->kn.sweep_grid;
     }
     const int grid = std::min(vi->d.B, vi->pipe_grid);
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(vi->HWs), smem, vi->stream, tp.a, tp.b, 0, make_geo(vi), make_coef<T>(vi),
+    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(vi->plan.HWs), smem, vi->stream, tp.a, tp.b, 0, make_geo(vi), make_coef<T>(vi),
                           vi->d_cells, Vin, Vout, vi->d_shards, k, check_prev);
     MGDP_HIP(hipGetLastError());
     return 0;
@@ -624,10 +484,10 @@ int launch_sweep_t(mgdp_vi *vi, int k, int check_prev, bool policy) {
     TimedPair tp;
     if (int rc = timed_begin(vi, k, &tp)) return rc;
     if constexpr (MAP == MGDP_MAP_CELL) {
-        if (vi->sweep_pipe == 1) return launch_sweep_pipe<T, MODEL, SLIP, 1>(vi, Vin, Vout, k, check_prev, tp);
-        if (vi->sweep_pipe == 2) return launch_sweep_pipe<T, MODEL, SLIP, 2>(vi, Vin, Vout, k, check_prev, tp);
-        if (vi->sweep_pipe == 3) return launch_sweep_pipe<T, MODEL, SLIP, 3>(vi, Vin, Vout, k, check_prev, tp);
-        if (vi->sweep_pipe == 4) return launch_sweep_pipe<T, MODEL, SLIP, 4>(vi, Vin, Vout, k, check_prev, tp);
+        if (vi->plan.sweep_pipe == 1) return launch_sweep_pipe<T, MODEL, SLIP, 1>(vi, Vin, Vout, k, check_prev, tp);
+        if (vi->plan.sweep_pipe == 2) return launch_sweep_pipe<T, MODEL, SLIP, 2>(vi, Vin, Vout, k, check_prev, tp);
+        if (vi->plan.sweep_pipe == 3) return launch_sweep_pipe<T, MODEL, SLIP, 3>(vi, Vin, Vout, k, check_prev, tp);
+        if (vi->plan.sweep_pipe == 4) return launch_sweep_pipe<T, MODEL, SLIP, 4>(vi, Vin, Vout, k, check_prev, tp);
     }
     return launch_sweep_kernel<T, MODEL, SLIP, MAP, false>(vi, Vin, Vout, k, check_prev, tp);
 }
@@ -652,15 +512,8 @@ int dispatch(mgdp_vi *vi, Args... args) {
 }
 
 template <typename T, int MODEL, bool SLIP, int MAP>
-struct FusedF {
-    static int run(mgdp_vi *vi, int k_target, unsigned long long *pub = nullptr, const long long *k_dev = nullptr,
-                   unsigned long long *mirror = nullptr) {
-        return launch_fused_t<T, MODEL, SLIP, MAP>(vi, k_target, pub, k_dev, mirror);
-    }
-};
-template <typename T, int MODEL, bool SLIP, int MAP>
-struct ServeF {
-    static int run(mgdp_vi *vi, unsigned int served) { return launch_serve_t<T, MODEL, SLIP, MAP>(vi, served); }
+struct ResolveF {
+    static int run(mgdp_vi *vi) { return resolve_kernels<T, MODEL, SLIP, MAP>(vi->plan, &vi->k); }
 };
 template <typename T, int MODEL, bool SLIP, int MAP>
 struct SweepF {
@@ -705,7 +558,7 @@ int reduce_env(mgdp_vi *vi, int32_t *kmax, double *dvmax) {
                 if (served && relaunches < 4) {
                     ++relaunches;
                     DeviceGuard guard(vi->d.device);  // the served fast path of mgdp_vi_solve holds none
-                    if (int rc = dispatch<ServeF>(vi, vi->epoch - 1u)) return rc;
+                    if (int rc = launch_serve(vi, vi->epoch - 1u)) return rc;
                     continue;
                 }
                 MGDP_CHECK(false, MGDP_E_HIP, "fused launch finished without publishing its result (epoch %u)", vi->epoch);
@@ -750,19 +603,17 @@ int reduce_env(mgdp_vi *vi, int32_t *kmax, double *dvmax) {
     return 0;
 }
 
-// Persistent solver hand-off (lone grid on the one-thread-per-cell fused path).
-bool serve_eligible(const mgdp_vi *vi) {
-    return vi->persistent && !vi->opts && vi->d.method == MGDP_METHOD_FUSED && vi->d.B == 1 && vi->d.mapping == MGDP_MAP_CELL &&
-           (vi->HW <= vi->cpt * vi->fused_block || vi->wave_p || vi->band) && !vi->pair && !vi->quad;
-}
+// Persistent solver hand-off (lone grid on the one-thread-per-cell fused path; the shape is the plan's).
+bool serve_eligible(const mgdp_vi *vi) { return vi->kn.persistent && vi->plan.serve_shape; }
 // The resident batch server (vi_bserve_kernel): a deterministic XYD batch on one wave per grid
 // (the wave2 kernel with its in-launch reduction) that fits the server's resident capacity, solved
 // with launch timing off (a timed solve is a launch, so kernel_time() keeps timing one solve per
-// launch), from V_0 = 0 under the own rule with at least one sweep.
+// launch), from V_0 = 0 under the own rule with at least one sweep.  Its buffers exist only where
+// the plan wants a batch server and it has a resident capacity.
 bool bserve_eligible(const mgdp_vi *vi) {
-    return vi->persistent && vi->bserve && vi->d_breq && vi->d_gk && !vi->timing && vi->d.B > 1 &&
-           (vi->d.B <= vi->bserve_cap || vi->bserve_any) &&
-           !vi->opts && vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0 && vi->d.max_sweeps >= 1;
+    return vi->kn.persistent && vi->d_breq && vi->d_gk && !vi->timing && vi->d.B > 1 &&
+           (vi->d.B <= vi->plan.bserve_cap || vi->plan.bserve_any) &&
+           !vi->plan.opts && vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0 && vi->d.max_sweeps >= 1;
 }
 bool served_eligible(const mgdp_vi *vi) { return serve_eligible(vi) || bserve_eligible(vi); }
 // Ask a resident server to leave and drain the stream.  Every entry point that enqueues other
@@ -853,7 +704,7 @@ int serve_request(mgdp_vi *vi) {
     post_request(vi);
     if (!vi->serving) {
         vi->exiting = false;  // a departing earlier server is no longer the stream's last work
-        if (int rc = dispatch<ServeF>(vi, vi->epoch - 1u)) return rc;
+        if (int rc = launch_serve(vi, vi->epoch - 1u)) return rc;
         vi->serving = true;
     }
     vi->fresh = 0;
@@ -975,233 +826,44 @@ int mgdp_vi_create(const mgdp_vi_desc *desc, mgdp_vi **out) {
     vi->HW = d.W * d.H;
     vi->HWp = (int)round_up(vi->HW, 16);
     vi->S = vi->HW * (d.model == MGDP_MODEL_XYD ? 4 : 16);
-    vi->HWs = vi->HW <= 1024 ? (int)round_up(vi->HW, 64) : vi->HW;
-    vi->Ss = vi->S / vi->HW * vi->HWs;
     vi->A = d.model == MGDP_MODEL_XYD ? 7 : 5;
     vi->tsize = d.dtype == MGDP_F32 ? 4 : 8;
-    // Two-sweep XYD step (3 LDS buffers): halves the barriers of the fused loop at 1.5x the VALU
-    // work.  Off by default (MGDP_PAIR=1 enables it; tests cover both steps).
-    {
-        const bool eligible = d.model == MGDP_MODEL_XYD && d.mapping == MGDP_MAP_CELL && vi->HW <= 1024;
-        int pair = 0;  // measured slower than the one-sweep step on MI355X (VALU chain, not barriers, bound it)
-        if (const char *ev = std::getenv("MGDP_PAIR")) pair = std::atoi(ev);
-        vi->pair = eligible && pair ? 1 : 0;
-        // Four threads per cell (one per direction, DPP quad exchange): MGDP_QUAD=1 enables it
-        // for grids with <= 256 cells (tests cover it).
-        int quad = 0;  // measured slower than one thread per cell (LDS/barrier latency bound it)
-        if (const char *ev = std::getenv("MGDP_QUAD")) quad = std::atoi(ev);
-        vi->quad = eligible && !vi->pair && quad && 4 * vi->HW <= 1024 ? 1 : 0;
-        vi->opts = d.horizon > 0 || d.lava_mode != MGDP_LAVA_TERMINAL;
-        if (vi->opts) vi->pair = vi->quad = 0;  // the options kernel runs the direction-major path only
-        vi->nbuf = vi->pair ? 3 : 2;
-    }
-    const Smem L = smem_layout(vi->Ss, vi->HWp, vi->tsize, vi->nbuf);
-    if (L.total() > 160 * 1024) {
+    // what runs: the knobs, the plan (vi_plan.h: the one place the variants' precedence is written),
+    // its kernels, and the two numbers that need the device
+    vi->kn = read_knobs();
+    vi->plan = plan_vi(d, vi->kn);
+    vi->serve_idle_ticks = (unsigned long long)vi->kn.serve_idle_us * 100ull;  // s_memrealtime ticks at 100 MHz
+    vi->serve_life_ticks = (unsigned long long)vi->kn.serve_life_us * 100ull;
+    const ViPlan &p = vi->plan;
+    if (p.lds_base > 160 * 1024) {
         delete vi;
-        set_error("grid too large for the LDS-resident kernels (%d B > 160 KiB)", L.total());
+        set_error("grid too large for the LDS-resident kernels (%d B > 160 KiB)", p.lds_base);
         return MGDP_E_UNSUPPORTED;
     }
-    // fused: one workgroup per grid.  MAP_CELL: one thread per cell (register topology) when the
-    // grid has <= 1024 cells; MAP_SA: 8 lanes per state, a lone grid gets the widest workgroup.
-    if (d.mapping == MGDP_MAP_CELL) {
-        vi->fused_block = (int)std::min<int64_t>(1024, round_up(vi->HW * (vi->quad ? 4 : 1), 64));
-        // A lone XYD grid of <= 64*MGDP_WAVE cells runs on ONE wave, P = 1, 2, 4 or 8 cells per
-        // lane: no workgroup barrier per sweep, the stopping rule is a wave ballot.  Measured per
-        // sweep against the multi-wave loop: P = 1 faster (0.10 vs 0.12 us), P = 2 even, P = 4 and 8
-        // slower (0.27 vs 0.17, 0.55 vs 0.18 us: one SIMD issues every cell's VALU work), so the
-        // default is P = 1 (grids of <= 64 cells); MGDP_WAVE=8 enables the rest (tests cover them).
-        int wave_max = 1;
-        if (const char *ev = std::getenv("MGDP_WAVE")) wave_max = std::atoi(ev);
-        if (d.B == 1 && d.model == MGDP_MODEL_XYD && d.method == MGDP_METHOD_FUSED && !vi->pair && !vi->quad &&
-            !vi->opts && vi->HW <= 64 * std::min(wave_max, 8)) {
-            int P = 1;
-            while (64 * P < vi->HW) P *= 2;
-            vi->wave_p = P;
-            vi->HWs = 64 * P;
-            vi->Ss = vi->S / vi->HW * vi->HWs;
-            vi->fused_block = 64;
+    if (int rc = dispatch<ResolveF>(vi)) {
+        delete vi;
+        return rc;
+    }
+    if (p.wants_gk) {  // resident workgroups of the one-wave launch and of the batch server running the same loop
+        int cus = 0, fused_per_cu = 0, bserve_per_cu = 0;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fused_per_cu, vi->k.to, p.block, p.lds) != hipSuccess) fused_per_cu = 0;
+        if (p.wants_bserve && hipOccupancyMaxActiveBlocksPerMultiprocessor(&bserve_per_cu, vi->k.bserve, 64, p.lds) != hipSuccess)
+            bserve_per_cu = 0;
+        resolve_residency(vi->plan, fused_per_cu, bserve_per_cu, cus);
+    }
+    if (d.method == MGDP_METHOD_FUSED && !p.opts) {  // more than 64 KiB of LDS is opted into once per kernel
+        hipError_t ea = hipSuccess;
+        auto big = [&](const void *k, int lds) {
+            if (ea == hipSuccess && lds > 64 * 1024) ea = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        };
+        big(vi->k.own, p.lds);
+        big(vi->k.to, p.lds);
+        if (p.serve_shape) big(vi->k.serve, p.serve_lds);
+        if (ea != hipSuccess) {
+            delete vi;
+            return hip_fail(ea, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", __FILE__, __LINE__);
         }
-        // Batched XYD grids: N cells per thread divides the waves per grid by N (MGDP_CPT=1|2|4;
-        // measured on MI355X, profiles/r01_cpt/: 2 beats 1 by 7-25 %).
-        int cpt = 2;
-        if (const char *ev = std::getenv("MGDP_CPT")) cpt = std::atoi(ev);
-        int lone_cpt = 1;  // a lone grid (latency) keeps one cell per thread unless MGDP_LONE_CPT=2
-        if (const char *ev = std::getenv("MGDP_LONE_CPT")) lone_cpt = std::atoi(ev) == 2 ? 2 : 1;
-        if (vi->wave_p) cpt = 1;
-        else if (d.B == 1) cpt = lone_cpt;
-        if ((cpt == 2 || cpt == 4) && d.model == MGDP_MODEL_XYD && d.method == MGDP_METHOD_FUSED &&
-            !vi->pair && !vi->quad && !vi->opts && vi->HW <= 1024) {
-            vi->cpt = cpt;
-            vi->fused_block = (int)round_up((vi->HW + cpt - 1) / cpt, 64);
-            vi->HWs = cpt * vi->fused_block;
-            vi->Ss = vi->S / vi->HW * vi->HWs;
-        }
-        if (const char *ev = std::getenv("MGDP_PAIR2")) vi->pair2 = std::atoi(ev) != 0;
-        // Batched deterministic XYD grids: one wave per grid, no workgroup barrier (fused_wave2_xyd)
-        // up to MGDP_WAVE2 cells per lane (0 disables it).
-        int wave2_max = 8;
-        if (const char *ev = std::getenv("MGDP_WAVE2")) wave2_max = std::atoi(ev);
-        const int P2 = (vi->HW + 63) / 64;
-        if (d.B > 1 && d.model == MGDP_MODEL_XYD && d.method == MGDP_METHOD_FUSED && d.slip_p < 0.0 && !vi->pair &&
-            !vi->quad && !vi->opts && !vi->wave_p && P2 <= std::min(wave2_max, 8)) {
-            vi->wave2 = P2;
-            vi->cpt = 1;
-            vi->fused_block = 64;
-            vi->HWs = (int)round_up(vi->HW, 64);
-            vi->Ss = vi->S / vi->HW * vi->HWs;
-        }
-        if (vi->wave2) {
-            int cus = 0;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
-            // Two waves per grid (MGDP_WAVE2N=1, grids of >= 3 blocks of 64 cells): measured slower
-            // than one wave per grid even where one wave per grid leaves the SIMDs short of waves --
-            // FourRooms x 4096: 64-65 us per solve (74 VGPRs, 6 waves / SIMD) or 57 us compiled for
-            // 8 waves / SIMD, vs 55-56 us on one wave (profiles/r04_w2nab/) -- so it is off by default.
-            int w2n = 0;
-            if (const char *ev = std::getenv("MGDP_WAVE2N")) w2n = std::atoi(ev) != 0 && vi->wave2 >= 3;
-            if (w2n) {
-                vi->wave2n = (vi->wave2 + 1) / 2;
-                vi->fused_block = 128;
-            }
-            if (const char *ev = std::getenv("MGDP_MIX"))
-                vi->mix = std::atoi(ev) != 0 && !vi->wave2n && d.dtype == MGDP_F32 && vi->wave2 >= 2 && vi->wave2 <= 6;
-            if (const char *ev = std::getenv("MGDP_MIX_FRAC")) vi->mix_frac = std::atof(ev);
-            if (vi->mix) vi->fused_block = 128;
-            // Column bands instead of row-major blocks (fused_band_xyd: north / south fronts in
-            // registers, no LDS tile): MGDP_BAND=1 (A/B; off by default until measured per size)
-            int band_on = 0;
-            if (const char *ev = std::getenv("MGDP_BAND")) band_on = std::atoi(ev);
-            const int hb = band_rows(d.W, d.H);
-            if (band_on && !vi->wave2n && !vi->mix && hb >= 1 && hb <= 8) vi->band = hb;
-            // The in-launch reduction (GkCtx) while the batch is resident at once (MGDP_GK=2, the
-            // default).  Since fixed-point completion no grid waits for another, so the counter tree
-            // would work for any B (MGDP_GK=1), but past the resident capacity every grid's exit
-            // waits for its counter's atomic while the next grid could start: LavaS11N5 x 65536
-            // 153 vs 144-145 us per launch, Empty-16 x 65536 314-319 vs 309-312
-            // (profiles/r05_mix/) -- the reduce kernel is cheaper there.  MGDP_GK=0: never.
-            int gk_on = 2;
-            if (const char *ev = std::getenv("MGDP_GK")) gk_on = std::atoi(ev);
-            const bool f32 = d.dtype == MGDP_F32;
-            const void *k2 = nullptr;
-            int smem2 = 0;
-            if (vi->band) {
-                smem2 = 256 + (vi->HWp + 15) / 16 * 16;
-                k2 = f32 ? (const void *)pick_band<FusedK, float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->band, FusedK<float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn)
-                         : (const void *)pick_band<FusedK, double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->band, FusedK<double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn);
-            } else if (vi->mix) {
-                smem2 = mix_smem_bytes(vi->HWp, d.W, vi->wave2, vi->tsize);
-                k2 = (const void *)pick_mix<FusedK, float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                    vi->wave2, FusedK<float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn);
-            } else if (vi->wave2n) {
-                smem2 = wave2n_smem_bytes(vi->HWp, d.W, 2 * vi->wave2n, vi->tsize);
-                k2 = f32 ? (const void *)pick_wave2n<FusedK, float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->wave2n, FusedK<float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn)
-                         : (const void *)pick_wave2n<FusedK, double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->wave2n, FusedK<double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn);
-            } else {
-                smem2 = wave2_smem_bytes(vi->HWp, d.W, vi->wave2, vi->tsize);
-                k2 = f32 ? (const void *)pick_wave2<FusedK, float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->wave2, FusedK<float, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn)
-                         : (const void *)pick_wave2<FusedK, double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL>(
-                               vi->wave2, FusedK<double, MGDP_MODEL_XYD, false, MGDP_MAP_CELL, 0>::fn);
-            }
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2, vi->fused_block, smem2) == hipSuccess)
-                vi->gk_capacity = per_cu * cus;
-            vi->gk = gk_on == 1 || (gk_on == 2 && d.B <= vi->gk_capacity);
-            // the resident batch server runs the same loop (wave2 layout, in-launch reduction)
-            if (const char *ev = std::getenv("MGDP_BSERVE")) {
-                vi->bserve = std::atoi(ev) != 0;
-                vi->bserve_any = std::atoi(ev) == 2;
-            }
-            if (const char *ev = std::getenv("MGDP_BSERVE_COPIES")) vi->bserve_copies = std::min(kBreqCopies, std::max(1, std::atoi(ev)));
-            if (const char *ev = std::getenv("MGDP_BSERVE_NAP")) vi->bserve_nap = std::min(64, std::max(0, std::atoi(ev)));
-            if (const char *ev = std::getenv("MGDP_BSERVE_WAIT_PUB")) vi->bserve_wait_pub = std::atoi(ev) != 0;
-            if (const char *ev = std::getenv("MGDP_BSERVE_PRIO_FRAC")) vi->bserve_prio_frac = std::min(1.0, std::max(0.0, std::atof(ev)));
-            if (vi->bserve && (vi->gk || vi->bserve_any) && !vi->band && !vi->mix && !vi->wave2n && d.slip_p < 0.0 && d.B > 1) {
-                const void *kb = f32 ? pick_bserve<float>(vi->wave2) : pick_bserve<double>(vi->wave2);
-                int per_cu = 0;
-                if (kb && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kb, 64, smem2) == hipSuccess)
-                    vi->bserve_cap = per_cu * cus;
-            }
-        }
-        // The served lone deterministic XYD grid: east / west fronts by DPP, <= 4 waves (one dword
-        // of stop flags); the two-plane padded tiles must fit the usual V buffers.
-        int serve_ew = 1;
-        if (const char *ev = std::getenv("MGDP_SERVE_EW")) serve_ew = std::atoi(ev);
-        const int padw = serve_ew_padw(d.W);
-        vi->serve_ew = serve_ew && d.B == 1 && d.model == MGDP_MODEL_XYD && d.method == MGDP_METHOD_FUSED &&
-                       d.slip_p < 0.0 && !vi->pair && !vi->quad && !vi->opts && !vi->wave_p && vi->cpt == 1 &&
-                       vi->fused_block <= 256 && vi->HWs >= vi->fused_block && 2 * vi->HWs >= 3 * padw;
-        // ... with two sweeps per workgroup barrier (fused_serve_pair): its two four-plane tiles take the
-        // first V buffers (nbuf raised to hold them; MGDP_SERVE_PAIR=0: off)
-        int serve_pair = 1;
-        if (const char *ev = std::getenv("MGDP_SERVE_PAIR")) serve_pair = std::atoi(ev);
-        if (vi->serve_ew && serve_pair) {
-            const int need = 2 * serve_pair_tile_elems(vi->HWs, d.W);
-            const int nbuf = std::max(2, (need + vi->Ss - 1) / vi->Ss);
-            if (smem_layout(vi->Ss, vi->HWp, vi->tsize, nbuf).total() <= 64 * 1024) {
-                vi->serve_pair = 1;
-                vi->nbuf = nbuf;
-            }
-        }
-        // The served lone deterministic XYD grid on ONE wave in column bands (fused_band_xyd: no
-        // barrier, no LDS tile; MGDP_SERVE_BAND=1, A/B)
-        int serve_band = 0;
-        if (const char *ev = std::getenv("MGDP_SERVE_BAND")) serve_band = std::atoi(ev);
-        const int hb1 = band_rows(d.W, d.H);
-        if (serve_band && d.B == 1 && d.model == MGDP_MODEL_XYD && d.method == MGDP_METHOD_FUSED && d.slip_p < 0.0 &&
-            !vi->pair && !vi->quad && !vi->opts && hb1 >= 1 && hb1 <= 8) {
-            vi->band = hb1;
-            vi->serve_ew = 0;
-            if (vi->serve_pair) vi->nbuf = 2;
-            vi->serve_pair = 0;
-            vi->wave_p = 0;
-            vi->cpt = 1;
-            vi->fused_block = 64;
-        }
-        int dk1t = 0;
-        if (const char *ev = std::getenv("MGDP_DK_1T")) dk1t = std::atoi(ev) != 0;
-        if (dk1t && d.B > 1 && d.model == MGDP_MODEL_DOORKEY && d.dtype == MGDP_F32 && d.method == MGDP_METHOD_FUSED &&
-            !vi->opts && vi->HW <= vi->fused_block) {
-            vi->dk1t = 1;
-            vi->nbuf = 1;  // one V tile in LDS
-        }
-        // Batched DoorKey grids of <= 512 cells: each cell's 16 states over two threads split by
-        // has_key (fused_dk_half).  Default for fp64 and for lone grids: measured on DoorKey-16
-        // (profiles/r02_dk_half/), x 65536 fp64 9.9e12 vs 2.8e12 updates/s (the one-thread-per-cell
-        // fp64 loop spills: 138 VGPRs of scratch) but fp32 1.90e13 vs 2.22e13 (the same 4 grids per
-        // CU, LDS-bound, with twice the LDS instructions); a lone grid, served: fp32 26.1 vs
-        // 28.4 us, fp64 34.8 vs 85.0 us per solve.  MGDP_DK_HALF=0|1 forces it off / on.
-        int dkhalf = (d.dtype == MGDP_F64 || d.B == 1) ? 1 : 0;
-        if (const char *ev = std::getenv("MGDP_DK_HALF")) dkhalf = std::atoi(ev) != 0;
-        if (dkhalf && !vi->dk1t && d.model == MGDP_MODEL_DOORKEY && d.method == MGDP_METHOD_FUSED &&
-            !vi->opts && vi->HW <= 512) {
-            vi->dkhalf = 1;
-            vi->HWs = (int)round_up(vi->HW, 64);
-            vi->Ss = vi->S / vi->HW * vi->HWs;
-            vi->fused_block = 2 * vi->HWs;
-        }
-        // Batched DoorKey grids of width 16 (DoorKey-16x16): whole grid rows per 16 lanes, east / west
-        // fronts by DPP, two conflict-free LDS planes (fused_dk_rows).  The special-first cell map of
-        // fused_fast_dk_soa spent half its LDS-array cycles on bank conflicts (round-4 counters).
-        // MGDP_DK_ROWS=0 keeps fused_fast_dk_soa.
-        int dkrow = 1;
-        if (const char *ev = std::getenv("MGDP_DK_ROWS")) dkrow = std::atoi(ev) != 0;
-        if (dkrow && !vi->dk1t && !vi->dkhalf && d.B > 1 && d.model == MGDP_MODEL_DOORKEY &&
-            d.method == MGDP_METHOD_FUSED && d.slip_p < 0.0 && !vi->opts && !vi->pair && !vi->quad && d.W == 16 &&
-            vi->HW <= 1024) {
-            vi->dkrow = 1;
-            vi->HWs = (int)round_up(vi->HW, 64);
-            vi->Ss = vi->S / vi->HW * vi->HWs;
-            vi->fused_block = vi->HWs;
-        }
-    } else {
-        int blk = d.B == 1 ? 1024 : 256;
-        while (blk > 64 && blk / 2 >= vi->S * 8) blk /= 2;
-        vi->fused_block = blk;
     }
 
     const size_t BS = (size_t)d.B * vi->S;
@@ -1218,11 +880,11 @@ int mgdp_vi_create(const mgdp_vi_desc *desc, mgdp_vi **out) {
     al((void **)&vi->d_shards, sizeof(unsigned long long) * 8 * (size_t)(d.max_sweeps + 1));
     al((void **)&vi->d_red, sizeof(unsigned long long) * (kRedShards * 4 + 2));
     al((void **)&vi->d_pub1, sizeof(unsigned long long) * 4);
-    if (vi->gk || (vi->bserve && vi->bserve_cap > 0 && vi->bserve_any)) {
+    if (vi->plan.gk || (vi->plan.bserve_cap > 0 && vi->plan.bserve_any)) {
         al((void **)&vi->d_gk, sizeof(unsigned long long) * gk_words(d.B));
         if (e == hipSuccess) e = hipMemset(vi->d_gk, 0, sizeof(unsigned long long) * gk_words(d.B));
     }
-    if (vi->bserve && vi->bserve_cap > 0 && (d.B <= vi->bserve_cap || vi->bserve_any)) {
+    if (vi->plan.bserve_cap > 0 && (d.B <= vi->plan.bserve_cap || vi->plan.bserve_any)) {
         al((void **)&vi->d_breq, sizeof(unsigned long long) * kBreqWords);
         if (e == hipSuccess) e = hipMemset(vi->d_breq, 0, sizeof(unsigned long long) * kBreqWords);
     }
@@ -1251,32 +913,6 @@ int mgdp_vi_create(const mgdp_vi_desc *desc, mgdp_vi **out) {
         vi->own_stream = e == hipSuccess;
     }
     if (e == hipSuccess) e = hipMemset(vi->d_cells, 0, (size_t)d.B * vi->HWp);
-    if (const char *ev = std::getenv("MGDP_SWEEP_M")) vi->sweep_m = std::max(1, std::atoi(ev));
-    // keep the staged group within the LDS budget (two groups per CU at least)
-    while (vi->sweep_m > 1 && sweep_smem_bytes(vi->S, vi->HWp, vi->tsize, vi->sweep_m) > 80 * 1024) --vi->sweep_m;
-    if (const char *ev = std::getenv("MGDP_SWEEP_GRID")) vi->sweep_grid = std::max(1, std::atoi(ev));
-    if (const char *ev = std::getenv("MGDP_SWEEP_BLOCK")) vi->sweep_block = std::min(256, std::max(64, std::atoi(ev) / 64 * 64));
-    if (const char *ev = std::getenv("MGDP_PERSISTENT")) vi->persistent = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_CHAIN")) vi->chain = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_LEARN_ORDER")) vi->learn_order = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_LEARN_PRIO")) vi->learn_prio = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_ORDER")) vi->order_src = std::strcmp(ev, "learned") == 0 ? 2 : (std::strcmp(ev, "off") == 0 ? 0 : 1);
-    if (const char *ev = std::getenv("MGDP_REDUCE_MULTI")) vi->reduce_multi = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_INKERNEL_MAX")) vi->inkernel_max = std::max(0, std::atoi(ev));
-    // DoorKey (64-128 B of V per thread) measured slower on the register pipeline (5.38 -> 3.3 TB/s
-    // compulsory: the prefetch registers collide with the 16-state backup's), so it keeps the
-    // staged kernel unless MGDP_SWEEP_PIPE asks otherwise.
-    if (d.model == MGDP_MODEL_DOORKEY) vi->sweep_pipe = 0;
-    if (const char *ev = std::getenv("MGDP_SWEEP_PIPE")) vi->sweep_pipe = std::min(4, std::max(0, std::atoi(ev)));
-    if (vi->HW > 1024 || d.mapping != MGDP_MAP_CELL ||
-        sweep_pipe_smem_bytes(vi->S, vi->HW, vi->HWs, vi->HWp, vi->tsize) > 160 * 1024)
-        vi->sweep_pipe = 0;  // one thread per cell: grids of <= 1024 cells
-    if (const char *ev = std::getenv("MGDP_SERVE_IDLE_US"))  // s_memrealtime ticks at 100 MHz
-        vi->serve_idle_ticks = (unsigned long long)std::max(1LL, std::atoll(ev)) * 100ull;
-    if (const char *ev = std::getenv("MGDP_SERVE_POLLERS")) vi->serve_pollers = std::max(1, std::atoi(ev));
-    if (const char *ev = std::getenv("MGDP_SERVE_POLL_DMA")) vi->serve_poll_dma = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("MGDP_SERVE_LIFE_US"))
-        vi->serve_life_ticks = (unsigned long long)std::max(1LL, std::atoll(ev)) * 100ull;
     if (vi->h_out) std::memset(vi->h_out, 0, kHoutWords * sizeof(unsigned long long));
     if (e == hipSuccess) {  // arm the fused reduction (every launch re-arms it for the next)
         std::vector<unsigned long long> init((size_t)kRedShards * 4 + 2, 0ull);
@@ -1415,16 +1051,16 @@ int set_order(mgdp_vi *vi, const std::vector<int32_t> &kx) {
     // mixed wave counts: the grids with keys >= mix_frac x the largest on two waves (they are the
     // first workgroups of the order just set)
     vi->nmix = 0;
-    if (vi->mix && kx[idx[0]] > 0) {
-        const int thr = std::max(1, (int)std::ceil(vi->mix_frac * kx[idx[0]]));
+    if ((vi->plan.kern == Loop::mix) && kx[idx[0]] > 0) {
+        const int thr = std::max(1, (int)std::ceil(vi->kn.mix_frac * kx[idx[0]]));
         while (vi->nmix < B && kx[idx[vi->nmix]] >= thr) ++vi->nmix;
     }
     vi->order_valid = true;
     return 0;
 }
 bool order_eligible(const mgdp_vi *vi) {
-    return vi->order_src != 0 && (vi->learn_order || vi->learn_prio) && vi->d.B >= kLearnMinB &&
-           vi->d.method == MGDP_METHOD_FUSED && !vi->opts && !serve_eligible(vi);
+    return vi->kn.order_src != 0 && (vi->kn.learn_order || vi->kn.learn_prio) && vi->d.B >= kLearnMinB &&
+           vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts && !serve_eligible(vi);
 }
 // order_src 2: from the executed sweeps of the previous solve
 int learn_dispatch(mgdp_vi *vi) {
@@ -1435,7 +1071,7 @@ int learn_dispatch(mgdp_vi *vi) {
 }
 // order_src 1: from the cells just loaded (one small launch, a D2H copy of B words and a sort)
 int cells_dispatch(mgdp_vi *vi) {
-    if (!order_eligible(vi) || vi->order_src != 1 || vi->HW > kDepthMaxHW) return 0;
+    if (!order_eligible(vi) || vi->kn.order_src != 1 || vi->HW > kDepthMaxHW) return 0;
     int32_t *d_depth = nullptr;
     MGDP_HIP(hipMallocAsync((void **)&d_depth, sizeof(int32_t) * (size_t)vi->d.B, vi->stream));
     hipLaunchKernelGGL(vi_depth_kernel, dim3(vi->d.B), dim3(64), 0, vi->stream, make_geo(vi),
@@ -1453,7 +1089,7 @@ int cells_dispatch(mgdp_vi *vi) {
 int mgdp_vi_reset(mgdp_vi *vi) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(vi->d.device);
-    if (!vi->order_valid && vi->order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi)) {
+    if (!vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi)) {
         if (int rc = server_stop(vi)) return rc;
         if (int rc = learn_dispatch(vi)) return rc;
     }
@@ -1487,7 +1123,7 @@ int mgdp_vi_run_local(mgdp_vi *vi, int32_t *k_local_max) {
             if (int rc = server_stop(vi)) return rc;
             // a finite horizon is exactly H backward sweeps from V_H = 0
             if (vi->d.horizon > 0) MGDP_CHECK(vi->fresh, MGDP_E_INVALID, "finite horizon: call mgdp_vi_reset first");
-            if (int rc = dispatch<FusedF>(vi, vi->d.horizon > 0 ? vi->d.horizon : -1)) return rc;
+            if (int rc = launch_fused(vi, vi->d.horizon > 0 ? vi->d.horizon : -1)) return rc;
         }
         int32_t km;
         if (int rc = reduce_env(vi, &km, nullptr)) return rc;
@@ -1521,7 +1157,7 @@ int mgdp_vi_run_to(mgdp_vi *vi, int32_t k_target, double *dv_out) {
         MGDP_CHECK(vi->d.horizon == 0, MGDP_E_INVALID,
                    "finite horizon: the DP is exactly H sweeps (mgdp_vi_run_local / mgdp_vi_solve)");
         if (int rc = server_stop(vi)) return rc;
-        if (int rc = dispatch<FusedF>(vi, k_target)) return rc;
+        if (int rc = launch_fused(vi, k_target)) return rc;
         int32_t km;
         if (int rc = reduce_env(vi, &km, dv_out)) return rc;
         MGDP_CHECK(km == k_target, MGDP_E_INVALID, "run_to(%d): a grid is already at sweep %d", k_target, km);
@@ -1546,27 +1182,27 @@ int mgdp_vi_run_to(mgdp_vi *vi, int32_t k_target, double *dv_out) {
 int mgdp_vi_run_local_dev(mgdp_vi *vi, int64_t *d_pub) {
     MGDP_CHECK(vi && d_pub, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
-    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->opts, MGDP_E_UNSUPPORTED,
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the device protocol runs the fused method without horizon / lava options");
     DeviceGuard guard(vi->d.device);
     if (int rc = server_stop(vi)) return rc;
     vi->k_done_valid = false;
-    return dispatch<FusedF>(vi, -1, reinterpret_cast<unsigned long long *>(d_pub), (const long long *)nullptr);
+    return launch_fused(vi, -1, reinterpret_cast<unsigned long long *>(d_pub), (const long long *)nullptr);
 }
 
 int mgdp_vi_run_to_dev(mgdp_vi *vi, const int64_t *d_k, int64_t *d_pub) {
     MGDP_CHECK(vi && d_k && d_pub, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->opts, MGDP_E_UNSUPPORTED,
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the device protocol runs the fused method without horizon / lava options");
     MGDP_CHECK(!vi->fresh, MGDP_E_INVALID, "mgdp_vi_run_to_dev before mgdp_vi_run_local_dev");
     DeviceGuard guard(vi->d.device);
     vi->k_done_valid = false;
-    return dispatch<FusedF>(vi, 0, reinterpret_cast<unsigned long long *>(d_pub), reinterpret_cast<const long long *>(d_k));
+    return launch_fused(vi, 0, reinterpret_cast<unsigned long long *>(d_pub), reinterpret_cast<const long long *>(d_k));
 }
 
 int mgdp_vi_run_to_dev_sync(mgdp_vi *vi, const int64_t *d_kdv, int32_t *k_out, double *dv_out, double *dv_rule_out) {
     MGDP_CHECK(vi && d_kdv, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->opts, MGDP_E_UNSUPPORTED,
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the device protocol runs the fused method without horizon / lava options");
     MGDP_CHECK(!vi->fresh, MGDP_E_INVALID, "mgdp_vi_run_to_dev_sync before mgdp_vi_run_local_dev");
     DeviceGuard guard(vi->d.device);
@@ -1583,7 +1219,7 @@ int mgdp_vi_run_to_dev_sync(mgdp_vi *vi, const int64_t *d_kdv, int32_t *k_out, d
     if (int rc = reduce_env(vi, &km, &dv)) return rc;
     if (vi->k_min != km) {
         // result -> host-mapped words (reduce_env polls them), d_kdv[1] -> h_out[12..13] by the launch
-        if (int rc = dispatch<FusedF>(vi, 0, (unsigned long long *)nullptr, reinterpret_cast<const long long *>(d_kdv),
+        if (int rc = launch_fused(vi, 0, (unsigned long long *)nullptr, reinterpret_cast<const long long *>(d_kdv),
                                       vi->d_hout + 12))
             return rc;
         if (int rc = reduce_env(vi, &km, &dv)) return rc;
@@ -1662,7 +1298,7 @@ int mgdp_vi_solve(mgdp_vi *vi, int32_t *sweeps_out, double *dv_out, int32_t *con
     // steady state makes no HIP call at all (no device guard either); anything else -- a server
     // that may be leaving, a rounding-level fallback sweep -- takes the general path below.
     // (a batch whose learned dispatch order is due takes the general path: mgdp_vi_reset learns it)
-    const bool learn_due = vi->d.B > 1 && !vi->order_valid && vi->order_src == 2 && vi->solves_since_load > 0;
+    const bool learn_due = vi->d.B > 1 && !vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0;
     if (vi->serving && served_eligible(vi) && vi->d.horizon == 0 && !learn_due) {
         const double idle_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - vi->serve_last).count();
         if (idle_us * 100.0 <= 0.5 * (double)vi->serve_idle_ticks) {
@@ -1709,15 +1345,15 @@ int mgdp_vi_solve(mgdp_vi *vi, int32_t *sweeps_out, double *dv_out, int32_t *con
     // Deterministic batches take the plain path: their grids end their own rule at exact fixed
     // points, so run_local's result completes the solve (run_to launches nothing, see
     // mgdp_vi_run_to) -- one launch and one wait.  Slip batches keep the chained pair.
-    if (vi->chain && !vi->gk && vi->d.slip_p >= 0.0 && vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0 &&
-        !vi->opts && !serve_eligible(vi)) {
+    if (vi->kn.chain && !vi->plan.gk && vi->d.slip_p >= 0.0 && vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0 &&
+        !vi->plan.opts && !serve_eligible(vi)) {
         // The single-GPU form of the multi-GPU device protocol: run_local publishes {K, ...} to
         // device memory and run_to(K) reads K there, enqueued back to back -- no host round trip
         // and no launch gap between the two; the host waits once, for run_to's result.
         DeviceGuard guard(vi->d.device);
         if (int rc = server_stop(vi)) return rc;
-        if (int rc = dispatch<FusedF>(vi, -1, vi->d_pub1, (const long long *)nullptr)) return rc;
-        if (int rc = dispatch<FusedF>(vi, 0, (unsigned long long *)nullptr, (const long long *)vi->d_pub1)) return rc;
+        if (int rc = launch_fused(vi, -1, vi->d_pub1, (const long long *)nullptr)) return rc;
+        if (int rc = launch_fused(vi, 0, (unsigned long long *)nullptr, (const long long *)vi->d_pub1)) return rc;
         if (int rc = reduce_env(vi, &k, &dv)) return rc;
         // run_to read K on the device: every grid must have ended exactly there (the host path's
         // km == k_target check)
@@ -1768,7 +1404,7 @@ int comm_max_double(mgdp_comm *c, hipStream_t s, double *x) {
 
 int mgdp_vi_solve_sharded(mgdp_vi *vi, mgdp_comm *comm, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
     MGDP_CHECK(vi && comm, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->opts, MGDP_E_UNSUPPORTED,
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the sharded solve runs the fused method without horizon / lava options");
     MGDP_CHECK(comm_device(comm) == vi->d.device, MGDP_E_INVALID, "communicator on device %d, handle on device %d",
                comm_device(comm), vi->d.device);
@@ -1873,37 +1509,12 @@ int mgdp_vi_persistent(const mgdp_vi *vi, int32_t *on) {
 
 const char *mgdp_vi_kernel_name(const mgdp_vi *vi) {
     if (!vi) { set_error("null handle"); return nullptr; }
-    if (vi->d.method == MGDP_METHOD_FUSED) {
-        if (vi->opts) return "vi_fused_opts_kernel";
-        return serve_eligible(vi) ? "vi_serve_kernel" : "vi_fused_kernel";
-    }
-    return vi->d.mapping == MGDP_MAP_CELL && vi->sweep_pipe ? "vi_sweep_pipe_kernel" : "vi_sweep_kernel";
+    return kernel_name(vi->plan, serve_eligible(vi));
 }
 
 const char *mgdp_vi_variant(const mgdp_vi *vi) {
     if (!vi) { set_error("null handle"); return nullptr; }
-    if (vi->d.method != MGDP_METHOD_FUSED) return vi->d.mapping == MGDP_MAP_CELL && vi->sweep_pipe ? "sweep_pipe" : "sweep";
-    if (vi->opts) return "opts";
-    if (vi->d.mapping == MGDP_MAP_SA) return "sa";
-    if (serve_eligible(vi)) {
-        if (vi->dkhalf) return "serve_dk_half";
-        if (vi->band) return "serve_band";
-        if (vi->serve_ew) return vi->serve_pair ? "serve_pair" : "serve_ew";
-        return vi->wave_p ? "serve_wave" : "serve";
-    }
-    if (vi->dkrow) return "dk_rows";
-    if (vi->dkhalf) return "dk_half";
-    if (vi->dk1t) return "dk_1t";
-    if (vi->band) return "band";
-    if (vi->mix) return "mix";
-    if (vi->wave2n) return "wave2n";
-    if (vi->wave2) return "wave2";
-    if (vi->wave_p) return "wave";
-    if (vi->pair) return "pair";
-    if (vi->quad) return "quad";
-    if (vi->cpt == 2) return vi->pair2 && vi->d.slip_p < 0.0 ? "xyd_pair2" : "xyd_x2";
-    if (vi->cpt == 4) return "xyd_x4";
-    return vi->d.model == MGDP_MODEL_DOORKEY ? "dk_soa" : "xyd_soa";
+    return variant_name(vi->plan, serve_eligible(vi));
 }
 
 int mgdp_vi_get_values(mgdp_vi *vi, void *V) {

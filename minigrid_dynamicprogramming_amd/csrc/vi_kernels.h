@@ -5,44 +5,27 @@
 #pragma once
 
 namespace mgdp {
-constexpr int kWpDk1t = -100;  // vi_fused_kernel variant tag: batched DoorKey on one LDS tile
-// vi_fused_kernel variant tag: batched DoorKey grids of width 16 on whole-row thread maps, DPP
-// east / west fronts and two conflict-free LDS planes (fused_dk_rows; its own LDS layout, dkrow_*)
-constexpr int kWpDkRow = -800;
-// ... the same for exactly 16x16 cells (DoorKey-16x16: 256 threads, plane stride known at compile time,
-// so one LDS base register serves every tile access) and own-rule launches only (one copy of the sweep
-// loops: the run_to copy kept values live across both).  Both are what let the fp32 loop fit 80 VGPRs
-// -- 6 waves per SIMD -- with no scratch (round 5's 6-wave build spilled 76 B per thread).
-constexpr int kWpDkRow16 = -801;
-__host__ __device__ constexpr bool wp_is_dkrow(int wp) { return wp == kWpDkRow || wp == kWpDkRow16; }
-// vi_fused_kernel variant tag: the direction-major one-thread-per-cell path alone.  The generic
-// variant (WP = 0) also holds the cell-major, pair and quad loops, and a kernel's VGPR budget is
-// that of its hungriest path: stripping them is what sets the batched kernels' occupancy.
-constexpr int kWpSoa = -200;
-// Tags -301 .. -308: batched deterministic XYD, two adjacent cells per thread, plane stride
-// HWS = 128 * (-tag - 300) known at compile time (fused_pair_xyd).
-constexpr int kWpPair = -300;
-__host__ __device__ constexpr bool wp_is_pair(int wp) { return wp <= kWpPair - 1 && wp >= kWpPair - 8; }
-// Tags -401 .. -408: batched deterministic XYD, one wave per grid, P = -tag - 400 cells per lane
-// (fused_wave2_xyd, its own compact LDS layout; vi_fused_kernel only).
-constexpr int kWpWave2 = -400;
-__host__ __device__ constexpr bool wp_is_wave2(int wp) { return wp <= kWpWave2 - 1 && wp >= kWpWave2 - 8; }
-// Tags -901 .. -908: batched deterministic XYD, one wave per grid in column bands of HB = -tag - 900
-// rows (fused_band_xyd; no LDS tile, vi_fused_kernel only).
-constexpr int kWpBand = -900;
-__host__ __device__ constexpr bool wp_is_band(int wp) { return wp <= kWpBand - 1 && wp >= kWpBand - 8; }
-// Tags -702 .. -704: batched deterministic XYD, TWO waves per grid, PW = -tag - 700 blocks of 64
-// cells per wave (fused_wave2n_xyd; 128-thread workgroups, vi_fused_kernel only).
-constexpr int kWpWave2n = -700;
-__host__ __device__ constexpr bool wp_is_wave2n(int wp) { return wp <= kWpWave2n - 2 && wp >= kWpWave2n - 4; }
-// Tags -1002 .. -1006 (fp32): batched deterministic XYD, P = -tag - 1000 blocks of 64 cells, 128-thread
-// workgroups with MIXED wave counts: the first Geo::nmix workgroups of the learned dispatch order
-// (the grids whose previous solve ran longest) sweep on two waves (fused_wave2n_xyd, PW = ceil(P / 2)
-// blocks each), every other grid on one (fused_wave2_xyd; its second wave leaves at once).  For
-// batches whose launch is set by a long tail of slow grids (an 8-way LavaS11N5 shard: median 24
-// sweeps, max 47): splitting a long grid's sweep chain over two waves shortens the tail.
-constexpr int kWpMix = -1000;
-__host__ __device__ constexpr bool wp_is_mix(int wp) { return wp <= kWpMix - 2 && wp >= kWpMix - 6; }
+// vi_fused_kernel / vi_serve_kernel instantiations are named <Loop L, int N> (vi_plan.h): the loop
+// family and its size.  Notes on what the tags buy:
+//  * Loop::generic also holds the cell-major, pair and quad loops, and a kernel's VGPR budget is that
+//    of its hungriest path: Loop::xyd_soa / dk_soa (the direction-major one-thread-per-cell path
+//    alone) strip them, which is what sets the batched kernels' occupancy.
+//  * Loop::dk_rows16 is dk_rows for exactly 16x16 cells (DoorKey-16x16: 256 threads, plane stride known
+//    at compile time, so one LDS base register serves every tile access) and own-rule launches only
+//    (one copy of the sweep loops: the run_to copy kept values live across both).  Both are what let
+//    the fp32 loop fit 80 VGPRs -- 6 waves per SIMD -- with no scratch (round 5's 6-wave build spilled
+//    76 B per thread).
+//  * Loop::mix (fp32, N = 2..6 blocks of 64 cells, 128-thread workgroups): the first Geo::nmix
+//    workgroups of the learned dispatch order (the grids whose previous solve ran longest) sweep on two
+//    waves (fused_wave2n_xyd, PW = ceil(N / 2) blocks each), every other grid on one (fused_wave2_xyd;
+//    its second wave leaves at once).  For batches whose launch is set by a long tail of slow grids (an
+//    8-way LavaS11N5 shard: median 24 sweeps, max 47): splitting a long grid's sweep chain over two
+//    waves shortens the tail.
+//  * Loop::serve_ew falls back to fused_fast_xyd_soa for a grid whose wave edges do not allow it.
+__host__ __device__ constexpr bool loop_is_dkrow(Loop l) { return l == Loop::dk_rows || l == Loop::dk_rows16; }
+__host__ __device__ constexpr bool loop_is_serve_ew(Loop l) { return l == Loop::serve_ew || l == Loop::serve_pair; }
+// every instantiation but the generic one and the lone wave runs the direction-major path alone
+__host__ __device__ constexpr bool loop_is_soa_only(Loop l) { return l != Loop::generic && l != Loop::wave; }
 // Minimum waves per SIMD the one-wave kernels are compiled for.  Left alone, the fp32 P <= 2
 // variants (LavaS11N5: 121 cells) take 57 VGPRs but 106 SGPRs, and the SGPRs cap them at 7 waves
 // per SIMD (28 workgroups / CU, 7168 grids resident): 8 makes the compiler fit 8 waves' SGPRs too
@@ -64,7 +47,7 @@ __host__ __device__ constexpr bool wp_is_mix(int wp) { return wp <= kWpMix - 2 &
 // Minimum waves per SIMD of fp32 fused_dk_rows: round 5's 6 (80 VGPRs and 76-80 B of scratch, 6 grids per
 // CU) measured 1950-1960 vs 1992-1996 us per DoorKey-16 x 65536 solve at 5, neutral at 8192 grids
 // (profiles/r05_dkw6/), but its spill stores doubled the launch's HBM writes.  Now: the 16x16 own-rule
-// variant (kWpDkRow16) at 6 waves, 80 VGPRs, no scratch; the general one at 5 (96 VGPRs, no scratch).
+// variant (Loop::dk_rows16) at 6 waves, 80 VGPRs, no scratch; the general one at 5 (96 VGPRs, no scratch).
 // A/B builds: MGDP_DKROW16_MINW / MGDP_DKROW_MINW (1 = the compiler's choice).
 #ifndef MGDP_DKROW_MINW
 #define MGDP_DKROW_MINW 5
@@ -73,35 +56,26 @@ __host__ __device__ constexpr bool wp_is_mix(int wp) { return wp <= kWpMix - 2 &
 #define MGDP_DKROW16_MINW 6
 #endif
 template <typename T>
-__host__ __device__ constexpr int wave2_min_waves(int wp) {
-    return wp == kWpDkRow     ? (sizeof(T) == 4 ? MGDP_DKROW_MINW : 1)  // fp64 at 6 waves spills 492 B
-           : wp == kWpDkRow16 ? (sizeof(T) == 4 ? MGDP_DKROW16_MINW : 1)
-           : wp_is_wave2n(wp) ? MGDP_WAVE2N_MINW
-           : (MGDP_WAVE2_W8 && wp_is_mix(wp) && kWpMix - wp <= 2) ? 8
-           : (MGDP_WAVE2_W8 && wp_is_wave2(wp) && kWpWave2 - wp <= (sizeof(T) == 4 ? 2 : 1)) ? 8
-           : (MGDP_WAVE2_P4_W6 && wp_is_wave2(wp) && sizeof(T) == 4 && kWpWave2 - wp == 4) ? 6
-                                                                                            : 1;
+__host__ __device__ constexpr int wave2_min_waves(Loop l, int n) {
+    return l == Loop::dk_rows     ? (sizeof(T) == 4 ? MGDP_DKROW_MINW : 1)  // fp64 at 6 waves spills 492 B
+           : l == Loop::dk_rows16 ? (sizeof(T) == 4 ? MGDP_DKROW16_MINW : 1)
+           : l == Loop::wave2n    ? MGDP_WAVE2N_MINW
+           : (MGDP_WAVE2_W8 && l == Loop::mix && n <= 2) ? 8
+           : (MGDP_WAVE2_W8 && l == Loop::wave2 && n <= (sizeof(T) == 4 ? 2 : 1)) ? 8
+           : (MGDP_WAVE2_P4_W6 && l == Loop::wave2 && sizeof(T) == 4 && n == 4) ? 6
+                                                                                  : 1;
 }
-// vi_fused_kernel variant tag: batched DoorKey, a cell's states split over two threads by has_key
-// (fused_dk_half; workgroup = 2 * HWs threads)
-// Tags -501 .. -508: plane stride HWs = 64 * (-tag - 500) known at compile time.
-constexpr int kWpDkHalf = -500;
-// vi_serve_kernel variant tag: the served lone deterministic XYD grid on fused_serve_xyd (east / west
-// fronts by DPP; <= 4 waves), fused_fast_xyd_soa for a grid whose wave edges do not allow it
-constexpr int kWpServeEw = -600;
-// ... the same grids with two sweeps per workgroup barrier (fused_serve_pair, round 6)
-constexpr int kWpServePair = -601;
-__host__ __device__ constexpr bool wp_is_serve_ew(int wp) { return wp == kWpServeEw || wp == kWpServePair; }
+// Loop::dk_half: batched DoorKey, a cell's states split over two threads by has_key (fused_dk_half;
+// workgroup = 2 * HWs threads), plane stride HWs = 64 * N known at compile time.
 // MGDP_DK_PERM=0 (A/B builds): batched DoorKey grids keep thread t on cell t (no dk_class_perm)
 #ifndef MGDP_DK_PERM
 #define MGDP_DK_PERM 1
 #endif
-__host__ __device__ constexpr bool wp_is_dkhalf(int wp) { return wp <= kWpDkHalf - 1 && wp >= kWpDkHalf - 8; }
 template <typename T, int MODEL> struct TopoOf { using type = XydTopo<T>; };
 template <typename T> struct TopoOf<T, MGDP_MODEL_DOORKEY> { using type = DkTopo; };
 
 // pre: the cell topology a persistent server resolved once per residency (SERVED only)
-template <typename T, int MODEL, bool SLIP, int MAP, bool SERVED = false, int WP = 0>
+template <typename T, int MODEL, bool SLIP, int MAP, bool SERVED = false, Loop L = Loop::generic, int N = 0>
 __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, const uint8_t *__restrict__ cells,
                                            T *__restrict__ V, int8_t *__restrict__ pi, int32_t *__restrict__ kenv,
                                            double *__restrict__ dvenv, unsigned long long *__restrict__ host_out,
@@ -109,13 +83,13 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
                                            int &k, double &dvl, const typename TopoOf<T, MODEL>::type *pre = nullptr,
                                            unsigned long long *gk = nullptr, int ew = 0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Smem L = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
+    const Smem LY = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
     T *V0 = reinterpret_cast<T *>(smem);
-    T *V1 = reinterpret_cast<T *>(smem + L.v_bytes);
-    int8_t *pis = reinterpret_cast<int8_t *>(smem + L.pi_off());
-    uint8_t *cl = reinterpret_cast<uint8_t *>(smem + L.cells_off());
-    T *slots = reinterpret_cast<T *>(smem + L.slots_off());
-    uint8_t *flags = reinterpret_cast<uint8_t *>(smem + L.flags_off());
+    T *V1 = reinterpret_cast<T *>(smem + LY.v_bytes);
+    int8_t *pis = reinterpret_cast<int8_t *>(smem + LY.pi_off());
+    uint8_t *cl = reinterpret_cast<uint8_t *>(smem + LY.cells_off());
+    T *slots = reinterpret_cast<T *>(smem + LY.slots_off());
+    uint8_t *flags = reinterpret_cast<uint8_t *>(smem + LY.flags_off());
 
     // workgroup-uniform: in SGPRs (as VGPRs they stayed live across the sweep loops -- a register
     // pair the batched DoorKey loop at 80 VGPRs had to spill to scratch)
@@ -146,9 +120,9 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
     const bool work = k_target < 0 ? (!(k > 0 && dvl < geo.tol) && k < geo.max_sweeps) : (k < k_target);
     if (!work) return false;
     const long long vb = (long long)e * geo.S;
-    if constexpr (wp_is_mix(WP)) {  // two waves for the first nmix workgroups, one for the rest
+    if constexpr (L == Loop::mix) {  // two waves for the first nmix workgroups, one for the rest
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "mix: batched plain XYD");
-        constexpr int P = kWpMix - WP, PW = (P + 1) / 2;
+        constexpr int P = N, PW = (P + 1) / 2;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         T *tile = reinterpret_cast<T *>(smem + wave2_tile_off(geo.HWp));
@@ -179,9 +153,9 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
         return true;
     }
-    if constexpr (wp_is_wave2n(WP)) {  // two waves per grid: cells, then two N/S tiles (wave2n_*)
+    if constexpr (L == Loop::wave2n) {  // two waves per grid: cells, then two N/S tiles (wave2n_*)
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "wave2n: batched plain XYD");
-        constexpr int PW = kWpWave2n - WP;
+        constexpr int PW = N;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         __syncthreads();
@@ -203,10 +177,10 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
         return true;
     }
-    if constexpr (wp_is_band(WP)) {  // LDS: slots, then the cells (no tile); served: the server's staged cells
+    if constexpr (L == Loop::band) {  // LDS: slots, then the cells (no tile); served: the server's staged cells
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "band: plain XYD");
-        constexpr int HB = kWpBand - WP;
-        uint8_t *cl2 = SERVED ? reinterpret_cast<uint8_t *>(smem + L.cells_off()) : smem + 256;
+        constexpr int HB = N;
+        uint8_t *cl2 = SERVED ? reinterpret_cast<uint8_t *>(smem + LY.cells_off()) : smem + 256;
         if (!SERVED) {
             copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its LDS writes are ordered
@@ -231,9 +205,9 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
         return true;
     }
-    if constexpr (wp_is_wave2(WP)) {  // its own LDS layout (wave2_*): cells, then the N/S tile
+    if constexpr (L == Loop::wave2) {  // its own LDS layout (wave2_*): cells, then the N/S tile
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "wave2: batched plain XYD");
-        constexpr int P = kWpWave2 - WP;
+        constexpr int P = N;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its LDS writes are ordered
@@ -259,7 +233,7 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
         return true;
     }
-    if constexpr (wp_is_dkrow(WP)) {  // its own LDS layout (dkrow_*): slots, flags, row map, cells, tiles
+    if constexpr (loop_is_dkrow(L)) {  // its own LDS layout (dkrow_*): slots, flags, row map, cells, tiles
         static_assert(MODEL == MGDP_MODEL_DOORKEY && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "dkrow: batched DoorKey");
         uint8_t *cl2 = smem + dkrow_cells_off();
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
@@ -273,7 +247,7 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
                 publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
                         (unsigned long long)kk, epoch);
         };
-        if constexpr (WP == kWpDkRow16) {  // own-rule launches only (the host picks kWpDkRow for run_to)
+        if constexpr (L == Loop::dk_rows16) {  // own-rule launches only (the host picks Loop::dk_rows for run_to)
             fused_dk_rows<T, true, 256>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb, k,
                                         k_target, dvl, done2, tl);
         } else if (k_target < 0) {
@@ -290,14 +264,14 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
         return true;
     }
-    // WP == kWpDk1t: batched DoorKey on one LDS tile (fused_fast_dk_1t); other WP < 0: -WP cells per
-    // thread on the batched XYD direction-major path (fused_fast_xyd_soa_xn)
-    constexpr bool DK1T = WP == kWpDk1t;
-    constexpr bool SOA_ONLY = WP < 0;  // every negative tag runs the direction-major path alone
-    constexpr bool PAIR2 = wp_is_pair(WP);
-    constexpr bool DKHALF = wp_is_dkhalf(WP);
-    constexpr bool SERVE_EW = wp_is_serve_ew(WP);
-    constexpr int CPT = PAIR2 ? 2 : (WP < 0 && !DK1T && !DKHALF && !SERVE_EW && WP != kWpSoa ? -WP : 1);
+    // Loop::dk_1t: batched DoorKey on one LDS tile (fused_fast_dk_1t); Loop::xyd_x2 / xyd_x4: CPT cells
+    // per thread on the batched XYD direction-major path (fused_fast_xyd_soa_xn)
+    constexpr bool DK1T = L == Loop::dk_1t;
+    constexpr bool SOA_ONLY = loop_is_soa_only(L);
+    constexpr bool PAIR2 = L == Loop::xyd_pair2;
+    constexpr bool DKHALF = L == Loop::dk_half;
+    constexpr bool SERVE_EW = loop_is_serve_ew(L);
+    constexpr int CPT = PAIR2 || L == Loop::xyd_x2 ? 2 : (L == Loop::xyd_x4 ? 4 : 1);
     const bool fast = MAP == MGDP_MAP_CELL && geo.HW <= CPT * (int)blockDim.x;
     const bool soa = SOA_ONLY || (fast && !geo.pair && !geo.quad);
     if (!SERVED) copy16(cl, cells + (long long)e * geo.HWp, geo.HWp);
@@ -326,12 +300,12 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         }
     };
     const T *Vfinal = nullptr;
-    if constexpr (WP > 0) {  // lone XYD grid on one wave, WP cells per lane (host: B == 1, blockDim 64)
+    if constexpr (L == Loop::wave) {  // lone XYD grid on one wave, N cells per lane (host: B == 1, blockDim 64)
         static_assert(MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL, "one-wave path is XYD, cell mapping");
         if (SERVED || k_target < 0)
-            fused_wave_xyd<T, SLIP, true, WP>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
+            fused_wave_xyd<T, SLIP, true, N>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         else
-            fused_wave_xyd<T, SLIP, false, WP>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
+            fused_wave_xyd<T, SLIP, false, N>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         if (threadIdx.x == 0) {
             kenv[e] = k;
             if (geo.kexec) geo.kexec[e] = k;
@@ -342,11 +316,11 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
     if (SERVED || soa) {  // served lone grids are always on this path (serve_eligible): no other code in the server
         if constexpr (PAIR2) {
             static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "pair path: plain XYD");
-            constexpr int HWS = 128 * (kWpPair - WP);
+            constexpr int HWS = 128 * N;
             if (k_target < 0) fused_pair_xyd<T, true, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
             else fused_pair_xyd<T, false, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && DKHALF) {
-            constexpr int HWS = 64 * (kWpDkHalf - WP);
+            constexpr int HWS = 64 * N;
             if (k_target < 0) fused_dk_half<T, true, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
             else fused_dk_half<T, false, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && DK1T) {
@@ -354,10 +328,10 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
             else fused_fast_dk_1t<T, false>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         } else if constexpr (SERVE_EW) {
             static_assert(SERVED && MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "served plain XYD grid");
-            // ew: 0 = this grid falls back, 1 = fused_serve_xyd (kWpServePair: fused_serve_pair), 2 = the
+            // ew: 0 = this grid falls back, 1 = fused_serve_xyd (Loop::serve_pair: fused_serve_pair), 2 = the
             // same, first solve of the grid
             bool ran = false;
-            if constexpr (WP == kWpServePair) {
+            if constexpr (L == Loop::serve_pair) {
                 if (ew) {
                     fused_serve_pair<T>(geo, cf, V0, V0 + serve_pair_tile_elems(geo.HWs, geo.W), slots, flags,
                                         V + vb, V + vb, pi + vb, k, dvl, done, *pre, ew == 2);
@@ -380,7 +354,7 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
             else fused_fast_xyd_soa<T, SLIP, false>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
         } else {
             // batched grids: the special-first thread -> cell map (dk_class_perm) in the unused pi region
-            uint8_t *perm = (MGDP_DK_PERM && !SERVED && 2 * geo.HW + 16 + 128 <= L.pi_bytes)
+            uint8_t *perm = (MGDP_DK_PERM && !SERVED && 2 * geo.HW + 16 + 128 <= LY.pi_bytes)
                                 ? reinterpret_cast<uint8_t *>(pis) : nullptr;
             if (SERVED || k_target < 0)
                 fused_fast_dk_soa<T, true>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done,
@@ -439,10 +413,10 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
     }
 }
 
-// WP > 0: the one-wave lone-grid variant (fused_wave_xyd), 64 threads, so its WP cells per lane
+// Loop::wave: the one-wave lone-grid variant (fused_wave_xyd), 64 threads, so its N cells per lane
 // may use the whole register file.
-template <typename T, int MODEL, bool SLIP, int MAP, int WP = 0>
-__global__ void __launch_bounds__(WP > 0 || wp_is_wave2(WP) || wp_is_band(WP) ? 64 : (wp_is_wave2n(WP) || wp_is_mix(WP) ? 128 : 1024), wave2_min_waves<T>(WP))
+template <typename T, int MODEL, bool SLIP, int MAP, Loop L = Loop::generic, int N = 0>
+__global__ void __launch_bounds__(L == Loop::wave || L == Loop::wave2 || L == Loop::band ? 64 : (L == Loop::wave2n || L == Loop::mix ? 128 : 1024), wave2_min_waves<T>(L, N))
 vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__restrict__ V,
                 int8_t *__restrict__ pi, int32_t *__restrict__ kenv, double *__restrict__ dvenv,
                 unsigned long long *__restrict__ red, unsigned int *__restrict__ ticket,
@@ -450,11 +424,11 @@ vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__res
                 unsigned int epoch, const long long *__restrict__ k_target_dev,
                 unsigned long long *__restrict__ host_mirror, unsigned long long *__restrict__ gk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Smem L = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
-    constexpr bool kOwnLds = wp_is_wave2(WP) || wp_is_wave2n(WP) || wp_is_band(WP) || wp_is_mix(WP);  // wave2-family layouts, gk
-    T *slots = reinterpret_cast<T *>(smem + (kOwnLds || wp_is_dkrow(WP) ? 0 : L.slots_off()));
+    const Smem LY = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
+    constexpr bool kOwnLds = L == Loop::wave2 || L == Loop::wave2n || L == Loop::band || L == Loop::mix;  // wave2-family layouts, gk
+    T *slots = reinterpret_cast<T *>(smem + (kOwnLds || loop_is_dkrow(L) ? 0 : LY.slots_off()));
     // a one-wave grid of a mixed launch: its second wave leaves before touching anything
-    if constexpr (wp_is_mix(WP))
+    if constexpr (L == Loop::mix)
         if (threadIdx.x >= 64 && (int)blockIdx.x >= geo.nmix) return;
     // multi-GPU protocol (mgdp_vi_run_to_dev): the target sweep is the all-reduced K in device
     // memory, written by a collective ordered before this launch on the stream
@@ -468,10 +442,10 @@ vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__res
     }
     int k;
     double dvl;
-    // kWpDkRow: the wave index in an SGPR, for late_tid after the sweep loop (fused_dk_rows)
+    // Loop::dk_rows: the wave index in an SGPR, for late_tid after the sweep loop (fused_dk_rows)
     const int wvk = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const bool lone = in_kernel_reduce && gridDim.x == 1;
-    const bool work = fused_grid<T, MODEL, SLIP, MAP, false, WP>(geo, cf, cells, V, pi, kenv, dvenv, host_out, k_target,
+    const bool work = fused_grid<T, MODEL, SLIP, MAP, false, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, k_target,
                                                                  fresh, lone, epoch,
                                                                  geo.order ? (int)geo.order[blockIdx.x] : (int)blockIdx.x,
                                                                  k, dvl, nullptr,
@@ -480,7 +454,7 @@ vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__res
     const bool gk_pub = kOwnLds && gk != nullptr && k_target < 0 && !k_target_dev;
     if (in_kernel_reduce && !gk_pub)
         fused_reduce(red, ticket, host_out, k, dvl, reinterpret_cast<unsigned int *>(slots + 16), epoch, work,
-                     wp_is_dkrow(WP) ? late_tid(wvk) : (int)threadIdx.x);
+                     loop_is_dkrow(L) ? late_tid(wvk) : (int)threadIdx.x);
 }
 
 // Persistent solver for a lone grid: one workgroup stays resident and serves solve requests posted
@@ -536,10 +510,10 @@ __device__ __forceinline__ void poll_issue(const unsigned long long *src, unsign
         : "memory");
 }
 
-// (kWpServePair: <= 4 waves by the host's serve_ew rule, so its three register sets and halo state may
+// (Loop::serve_pair: <= 4 waves by the plan's serve_ew rule, so its three register sets and halo state may
 // use up to 512 VGPRs per lane: no spill)
-template <typename T, int MODEL, bool SLIP, int MAP, int WP = 0>
-__global__ void __launch_bounds__(WP > 0 ? 64 : (WP == kWpServePair ? 256 : 1024))
+template <typename T, int MODEL, bool SLIP, int MAP, Loop L = Loop::generic, int N = 0>
+__global__ void __launch_bounds__(L == Loop::wave ? 64 : (L == Loop::serve_pair ? 256 : 1024))
 vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict__ V,
                 int8_t *__restrict__ pi, int32_t *__restrict__ kenv, double *__restrict__ dvenv,
                 unsigned long long *__restrict__ host_out, const unsigned long long *__restrict__ host_cmd,
@@ -548,8 +522,8 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long s_cmd, s_src;
     __shared__ __attribute__((aligned(16))) unsigned long long s_box[2];  // poll mailbox: {request, source}
-    const Smem L = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
-    uint8_t *cl = reinterpret_cast<uint8_t *>(smem + L.cells_off());
+    const Smem LY = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
+    uint8_t *cl = reinterpret_cast<uint8_t *>(smem + LY.cells_off());
     copy16(cl, cells, geo.HWp);
     if (threadIdx.x == 0) {
         s_cmd = served;
@@ -566,16 +540,16 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
     __syncthreads();
     // the grid stays put between kServeNewCells requests: resolve this thread's cell topology once
     typename TopoOf<T, MODEL>::type topo;
-    int ew = 0;  // kWpServeEw: 0 = the grid falls back, 1 = fused_serve_xyd, 2 = the same, tiles to clear
+    int ew = 0;  // Loop::serve_ew: 0 = the grid falls back, 1 = fused_serve_xyd, 2 = the same, tiles to clear
     __shared__ int s_ew;
     auto resolve = [&]() {
-        if constexpr (WP == 0 || wp_is_serve_ew(WP)) {
+        if constexpr (L == Loop::generic || loop_is_serve_ew(L)) {
             const int cc = (int)threadIdx.x < geo.HW ? (int)threadIdx.x : 0;
             if constexpr (MODEL == MGDP_MODEL_XYD) topo = xyd_topo_soa<T>(cl, geo, cc);
             else topo = dk_topo_soa(cl, geo, cc);
         }
-        if constexpr (WP == kWpServePair && MODEL == MGDP_MODEL_XYD) topo.halo = serve_pair_halo(cl, geo, (int)threadIdx.x);
-        if constexpr (wp_is_serve_ew(WP)) ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
+        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) topo.halo = serve_pair_halo(cl, geo, (int)threadIdx.x);
+        if constexpr (loop_is_serve_ew(L)) ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
     };
     resolve();
     while (true) {
@@ -637,9 +611,9 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
         }
         int k;
         double dvl;
-        if (!fused_grid<T, MODEL, SLIP, MAP, true, WP>(geo, cf, cells, V, pi, kenv, dvenv, host_out, -1, 1, true,
+        if (!fused_grid<T, MODEL, SLIP, MAP, true, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, -1, 1, true,
                                                    (unsigned int)cmd, 0, k, dvl,
-                                                   (WP == 0 || wp_is_serve_ew(WP)) ? &topo : nullptr, nullptr, ew) &&
+                                                   (L == Loop::generic || loop_is_serve_ew(L)) ? &topo : nullptr, nullptr, ew) &&
             threadIdx.x == 0)
             publish_tagged(host_out, k, dvl, (unsigned int)cmd);
         if (ew == 2) ew = 1;  // the tiles' pads stay +0 until the next grid
@@ -689,7 +663,6 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
 // period, so every wave reaches the exit.  The last wave out (a two-level exit counter) writes the exit
 // word, as a lone server does.
 constexpr unsigned long long kBreqQuit = 1ull << 63;
-constexpr int kBreqCopies = 64;                                       // request lines (workgroup w polls w % copies)
 constexpr int kBreqExit = kBreqCopies * 16;                           // exit counters: 64 shard lines, then the top line
 constexpr int kBreqExitShards = 64;
 constexpr int kBreqWords = kBreqExit + (kBreqExitShards + 1) * 16;
@@ -721,7 +694,7 @@ __host__ __device__ constexpr int bserve_min_waves(int P) {
 // MULTI: the launch has fewer workgroups than grids (a batch past the resident capacity, MGDP_BSERVE=2):
 // its own instantiation, so the resident loop keeps its registers.
 template <typename T, int P, bool MULTI = false>
-__global__ void __launch_bounds__(64, MGDP_BSERVE_MINW ? bserve_min_waves<T>(P) : wave2_min_waves<T>(kWpWave2 - P))
+__global__ void __launch_bounds__(64, MGDP_BSERVE_MINW ? bserve_min_waves<T>(P) : wave2_min_waves<T>(Loop::wave2, P))
 vi_bserve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__restrict__ V,
                  int8_t *__restrict__ pi, int32_t *__restrict__ kenv, double *__restrict__ dvenv,
                  unsigned long long *__restrict__ host_out, const unsigned long long *__restrict__ host_cmd,
@@ -1194,10 +1167,6 @@ __device__ __forceinline__ bool prev_sweep_converged(const unsigned long long *s
 // ------------------------------------------------------------------------------------------------
 constexpr int kSweepBlock = 256;
 
-__host__ __device__ inline int sweep_smem_bytes(int S, int HWp, int tsize, int m) {
-    return 2 * m * S * tsize + m * ((S + 15) / 16 * 16) + m * HWp + 256;
-}
-
 template <typename T, int MODEL, bool SLIP, int MAP, bool POLICY>
 __global__ void __launch_bounds__(kSweepBlock)
 vi_sweep_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, const T *__restrict__ Vin,
@@ -1256,10 +1225,6 @@ struct PipeRow {
     V4<T> v[NV];
     uint32_t cw;  // cell bytes 4c .. 4c+3 (threads c < HWp/4)
 };
-
-__host__ __device__ inline int sweep_pipe_smem_bytes(int S, int HW, int HWs, int HWp, int tsize) {
-    return S / HW * HWs * tsize + HWp + 256;
-}
 
 // V is streamed once per sweep (Vin read, Vout written; the next sweep's Vin is the whole
 // 553 MB array again, far past the 256 MB MALL), so the loads and stores are nontemporal:

@@ -153,27 +153,7 @@ __device__ __forceinline__ void copy_pi(int8_t *dst, const int8_t *src, int S) {
     for (int i = threadIdx.x; i < (S >> 2); i += blockDim.x) d[i] = s[i];
 }
 
-struct Smem {
-    int nbuf, v_bytes, pi_bytes, cells_bytes, slot_bytes;
-    __host__ __device__ int total() const { return nbuf * v_bytes + pi_bytes + cells_bytes + slot_bytes; }
-    __host__ __device__ int pi_off() const { return nbuf * v_bytes; }
-    __host__ __device__ int cells_off() const { return nbuf * v_bytes + pi_bytes; }
-    __host__ __device__ int slots_off() const { return nbuf * v_bytes + pi_bytes + cells_bytes; }
-    __host__ __device__ int flags_off() const { return slots_off() + 256; }
-};
-
-__host__ __device__ inline Smem smem_layout(int S, int HWp, int tsize, int nbuf = 2) {
-    Smem m;
-    m.nbuf = nbuf;
-    m.v_bytes = S * tsize;  // S is a multiple of 4 -> 16-B multiple for f32, f64
-    m.pi_bytes = (S + 15) / 16 * 16;
-    m.cells_bytes = HWp;
-    m.slot_bytes = 256 + 64;  // block_max slots [2][16] x 8 B + convergence flags [2][2][16] B
-    return m;
-}
-
 constexpr int kRedShards = 64;  // fused-launch reduction shards: [64][kmax, dV bits, kmin, -]
-constexpr int kInKernelReduceMaxB = 512;  // above this, a separate one-workgroup reduce kernel
 
 // Fold this block's (k, dV) into the launch reduction.  Every access to the shards and the ticket
 // is an atomic read-modify-write (performed at the device coherence point, never served from a
@@ -404,7 +384,7 @@ __device__ __forceinline__ void fused_fast_xyd_soa(const Geo &geo, const Coef<T>
     }
 }
 
-// The served lone deterministic XYD grid (vi_serve_kernel, WP = kWpServeEw): fused_fast_xyd_soa's
+// The served lone deterministic XYD grid (vi_serve_kernel, Loop::serve_ew): fused_fast_xyd_soa's
 // sweep with a shorter per-sweep chain for a latency-bound workgroup of <= 4 waves.
 //  * East / west fronts by DPP: cell c +- 1 is lane +- 1 of the same wave (wave_shl / wave_shr,
 //    0 shifted in at the wave's ends), so only planes 1 and 3 (south / north fronts) go through
@@ -421,8 +401,6 @@ __device__ __forceinline__ void fused_fast_xyd_soa(const Geo &geo, const Coef<T>
 // Same backups (one-multiply form), same rule and the same per-action pi pass as fused_fast_xyd_soa:
 // bit-identical V, pi, sweep count and dV.  LDS: each tile = [pad][plane 1][pad][plane 3][pad]
 // (serve_ew_tile_elems), carved from the two V buffers of the usual layout.
-__host__ __device__ inline int serve_ew_padw(int W) { return (W + 15) / 16 * 16; }
-__host__ __device__ inline int serve_ew_tile_elems(int HWs, int W) { return 2 * HWs + 3 * serve_ew_padw(W); }
 
 template <typename T>
 __device__ __forceinline__ T dpp_shl1_zero(T v) {  // lane i <- lane i+1; lane 63 <- +0
@@ -586,7 +564,7 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
 }
 
 // The served lone deterministic XYD grid, TWO sweeps per workgroup barrier (vi_serve_kernel,
-// WP = kWpServePair; grids on <= 4 waves whose wave edges pass serve_ew_ok).  Round 6.  A lone grid's
+// Loop::serve_pair; grids on <= 4 waves whose wave edges pass serve_ew_ok).  Round 6.  A lone grid's
 // sweep is latency-bound: its LDS write -> s_barrier -> LDS read round trip and the stop test's
 // ballot / flag byte around it cost more than the arithmetic (tools/probe_sweep_chain.hip,
 // profiles/r06_dist/: 449 cycles per sweep with the round trip, 289 without the stop test).  Here a
@@ -617,9 +595,6 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
 //    pairs.  LDS: two tiles of four planes, each [pad][HWs cells][pad], pad = round_up(2W, 16), the
 //    host sizes the V buffers for them (serve_pair_tile_elems).
 // Requires k < max_sweeps on entry (fused_grid only calls with work to do).
-__host__ __device__ inline int serve_pair_pad(int W) { return (2 * W + 15) / 16 * 16; }
-__host__ __device__ inline int serve_pair_plane(int HWs, int W) { return HWs + 2 * serve_pair_pad(W); }
-__host__ __device__ inline int serve_pair_tile_elems(int HWs, int W) { return 4 * serve_pair_plane(HWs, W); }
 
 // The pair loop's neighbour topology of thread t (resolved once per grid by the server): bit 0 the
 // cell t + W is walkable, bit 1 a goal lies south of it (its plane 1 is then max(., 1)); bits 2 / 3
@@ -1049,11 +1024,6 @@ __device__ __forceinline__ void fused_pair_xyd(const Geo &geo, const Coef<T> &cf
 // fused_pair_xyd (invalid states hold +0); the stop rule is the wave's ballot.  Same backups,
 // rule and pi pass as fused_fast_xyd_soa: bit-identical V, pi and sweep counts.
 // LDS: [slots 256 B][cells HWp][tile: pad | plane 3 (64P) | plane 1 (64P) | pad] (wave2_* below).
-__host__ __device__ inline int wave2_padw(int W) { return (W + 15) / 16 * 16; }
-__host__ __device__ inline int wave2_tile_off(int HWp) { return 256 + (HWp + 15) / 16 * 16; }
-__host__ __device__ inline int wave2_smem_bytes(int HWp, int W, int P, int tsize) {
-    return wave2_tile_off(HWp) + (2 * 64 * P + 2 * wave2_padw(W)) * tsize;
-}
 // In-launch reduction of an own-rule launch (mgdp_vi_solve / run_local on a one-wave batch that is
 // resident at once; the host picks it then, else the reduce kernel follows the launch).  Each grid
 // wave, at its own stopping sweep k_e, stores {k_e, dV} to its slots and draws a ticket of one of
@@ -1071,17 +1041,6 @@ struct GkCtx {
     int B;                    // grids in the launch
     unsigned long long *pub;  // where the launch's {kmax, dV bits, kmin} go (host-mapped: epoch-tagged; device: raw)
 };
-constexpr int kGkShards = 256;
-constexpr int kGkLine = 16;                                    // u64 words per 128-B line
-constexpr int kGkCnt2 = 0;                                     // [256 shard counter lines][top line]
-constexpr int kGkTop2 = kGkCnt2 + kGkShards * kGkLine;
-constexpr int kGkSxMin = kGkTop2 + kGkLine;                    // int32 [256] shard min reported sweeps
-constexpr int kGkSxMax = kGkSxMin + kGkShards / 2;             // int32 [256] shard max reported sweeps
-constexpr int kGkSxDv = kGkSxMax + kGkShards / 2;              // u64 [256] shard max dV bits
-__host__ __device__ inline int gk_kr_off(int B) { (void)B; return kGkSxDv + kGkShards; }  // int32 [B] sweeps,
-__host__ __device__ inline int gk_dv_off(int B) { return gk_kr_off(B) + (B + 1) / 2; }     // u64 [B] dV bits
-__host__ __device__ inline int gk_kn_off(int B) { return gk_dv_off(B) + B; }               // int32 [B] min sweeps (KMIN)
-__host__ __device__ inline int gk_words(int B) { return gk_kn_off(B) + (B + 1) / 2; }
 
 __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
@@ -1419,7 +1378,6 @@ __device__ __forceinline__ T lane_shfl(T v, int src) {  // lane src's v (ds_bper
         return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
     }
 }
-__host__ __device__ inline int band_rows(int W, int H) { return W > 64 ? 0 : (H + 64 / W - 1) / (64 / W); }
 
 template <typename T, bool LOCAL, int HB, typename Done>
 __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf, const uint8_t *cl, const T *Vg,
@@ -1568,15 +1526,6 @@ __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf
 // ballot through a flag word per tile, read with the next sweep's fronts -- so both waves take
 // the same stop decision.  Arithmetic, rule and pi pass as fused_wave2_xyd: bit-identical results.
 // LDS: [slots 256 B][cells HWp][tile 0][tile 1][edges 4 T | dV 2 T | flags 4 u32] (wave2n_*).
-__host__ __device__ inline int wave2n_tile_elems(int W, int P) { return 2 * 64 * P + 2 * wave2_padw(W); }
-__host__ __device__ inline int wave2n_smem_bytes(int HWp, int W, int P, int tsize) {
-    return wave2_tile_off(HWp) + 2 * wave2n_tile_elems(W, P) * tsize + 64;
-}
-// A mixed launch (kWpMix): P blocks on one wave or 2 * ceil(P / 2) on two, the larger layout
-__host__ __device__ inline int mix_smem_bytes(int HWp, int W, int P, int tsize) {
-    const int a = wave2_smem_bytes(HWp, W, P, tsize), b = wave2n_smem_bytes(HWp, W, 2 * ((P + 1) / 2), tsize);
-    return a > b ? a : b;
-}
 
 template <typename T, bool LOCAL, int PW, typename Done>
 __device__ __forceinline__ void fused_wave2n_xyd(const Geo &geo, const Coef<T> &cf, const uint8_t *cl, T *tile,
@@ -2043,12 +1992,6 @@ __device__ __forceinline__ void fused_fast_dk_soa(const Geo &geo, const Coef<T> 
 // to fused_fast_dk_soa / the oracle.  LDS (dkrow_*): [slots 256][flags 64][row map 128][cells HWp]
 // [tile 0: plane 1 | plane 3][tile 1: ...], each plane PL = HWs + 32 V4 entries, cell c at 16 + c
 // (16 zero entries either side: the border rows' north / south reads land there).
-__host__ __device__ inline int dkrow_cells_off() { return 256 + 64 + 128; }
-__host__ __device__ inline int dkrow_tile_off(int HWp) { return dkrow_cells_off() + (HWp + 15) / 16 * 16; }
-__host__ __device__ inline int dkrow_plane(int HWs) { return HWs + 32; }  // V4 entries per plane
-__host__ __device__ inline int dkrow_smem_bytes(int HWp, int HWs, int tsize) {
-    return dkrow_tile_off(HWp) + 2 * 2 * dkrow_plane(HWs) * 4 * tsize;
-}
 
 // Value sweep of one DoorKey cell from geometric fronts (fE / fW: the east / west neighbours' plane
 // 0 / 2 values, fS / fN: the south / north neighbours' plane 1 / 3 groups).  Candidates per state as
@@ -2106,7 +2049,7 @@ __device__ __forceinline__ T dk_rows_step(uint32_t walk, const uint32_t (&f)[4],
     return vmax(vmax(vmax(a, b), c), vmax(vmax(e, h), df[15]));
 }
 
-// HWS_C: the workgroup size (HWs) when known at compile time (kWpDkRow16), else 0
+// HWS_C: the workgroup size (HWs) when known at compile time (Loop::dk_rows16), else 0
 template <typename T, bool LOCAL, int HWS_C = 0, typename Done>
 __device__ __forceinline__ void fused_dk_rows(const Geo &geo, const Coef<T> &cf, const uint8_t *cl, T *tiles,
                                               T *slots, uint8_t *flags, uint8_t *rowmap, const T *Vg, T *Vg_out,
