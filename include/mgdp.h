@@ -87,7 +87,9 @@ enum {
  *     V_H = 0, V_t = max_a Q_t with the exact time-dependent goal reward of _reward()
  *     (minigrid_env.py:235-240; step_count is incremented before it, :522; truncation at
  *     step_count >= max_steps, :582-583, is V_H = 0).  Exactly H backward sweeps, no stopping
- *     rule; V / pi report t = 0; flag MGDP_KEEP_POLICY_T keeps pi_t for every t. */
+ *     rule; V / pi report t = 0; flag MGDP_KEEP_POLICY_T keeps pi_t for every t.
+ *   Both options run one thread per cell in one workgroup: mgdp_vi_create refuses either with
+ *   W*H > 1024 (MGDP_E_UNSUPPORTED). */
 enum { MGDP_LAVA_TERMINAL = 0, MGDP_LAVA_NODEATH = 1 };
 enum { MGDP_KEEP_POLICY_T = 1 };
 

@@ -815,6 +815,9 @@ int mgdp_vi_create(const mgdp_vi_desc *desc, mgdp_vi **out) {
     MGDP_CHECK(!((d.horizon > 0 || d.lava_mode) && (d.method != MGDP_METHOD_FUSED || d.mapping != MGDP_MAP_CELL)),
                MGDP_E_UNSUPPORTED, "horizon / lava_mode options run on the fused MGDP_MAP_CELL path only");
     MGDP_CHECK(!(d.horizon > 0 && (long long)d.W * d.H > 1024), MGDP_E_UNSUPPORTED, "horizon needs W*H <= 1024");
+    // the options kernel is strictly one thread per cell (fused_fast_xyd_soa) in a workgroup of <= 1024
+    MGDP_CHECK(!(d.lava_mode == MGDP_LAVA_NODEATH && (long long)d.W * d.H > 1024), MGDP_E_UNSUPPORTED,
+               "NoDeath lava needs W*H <= 1024");
     int ndev = 0;
     MGDP_HIP(hipGetDeviceCount(&ndev));
     MGDP_CHECK(d.device >= 0 && d.device < ndev, MGDP_E_HIP, "device %d not available (%d visible)", d.device, ndev);

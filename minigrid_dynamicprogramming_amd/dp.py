@@ -142,7 +142,8 @@ class ValueIteration:
                  keep_policy_t: bool = False):
         """lava="nodeath": NoDeath(no_death_types=("lava",), death_cost) semantics
         (wrappers.py:799-872).  horizon=H > 0: finite-horizon DP over step_count with the exact
-        _reward() (minigrid_env.py:235-240), H = the env's max_steps; keep_policy_t keeps pi_t."""
+        _reward() (minigrid_env.py:235-240), H = the env's max_steps; keep_policy_t keeps pi_t.
+        Either option needs W*H <= 1024 (one thread per cell in one workgroup): ValueError above."""
         cells, enc = to_cells(grids)
         if model == "auto":
             model = infer_model(cells)

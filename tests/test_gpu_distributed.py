@@ -196,7 +196,7 @@ def test_device_protocol_rccl1_slip(B, mode):
 
 
 # -- mgdp_vi_solve_sharded at world > 1 on one GPU: the host communicator -----------------------------
-def _multi_worker(rank, world, port, env_id, B, dtype, slip, kinds, out):
+def _multi_worker(rank, world, port, env_id, B, dtype, slip, kinds, out, kw=None):
     """One rank: a gloo group for the bootstrap, the library's host communicator (mgdp_comm_create_host),
     and this rank's shard on the path its kind names: "lib" = a fused handle, one mgdp_vi_solve_sharded
     call per solve (the C code's collectives); "host" = a sweep-method handle driving the same
@@ -220,7 +220,8 @@ def _multi_worker(rank, world, port, env_id, B, dtype, slip, kinds, out):
     if kind == "empty":
         shard = EmptyShard()
     else:
-        shard = mg.ValueIteration(cells[lo:hi], dtype=dtype, slip_p=slip, method="fused" if kind == "lib" else "sweep")
+        shard = mg.ValueIteration(cells[lo:hi], dtype=dtype, slip_p=slip, method="fused" if kind == "lib" else "sweep",
+                                  **(kw or {}))
     res = []
     for _ in range(2):  # a second solve on the same communicator and handles
         r = solve_sharded(shard, comm=comm)
@@ -275,3 +276,28 @@ def test_solve_sharded_multi_rank_host_comm(env_id, B, dtype, slip, kinds):
             np.testing.assert_array_equal(V, o["V"][lo:hi])
             np.testing.assert_array_equal(pi, o["pi"][lo:hi])
     assert len(counts) == 1, counts  # every rank met the same collectives
+
+
+def test_solve_sharded_deterministic_grids_stopped_by_the_tolerance():
+    """The `rule != 0` side of mgdp_vi_solve_sharded on deterministic grids: at gamma 0.5, tol 1e-3 the
+    FourRooms grids stop their own rule at sweep 11 with dV = 2^-10 > 0 (no exact fixed point, which is
+    where every deterministic grid ends at gamma 0.99), so E != 0 and dV(K) is all-reduced as for slip."""
+    from oracle import oracle
+    from minigrid_dynamicprogramming_amd import gen
+
+    env_id, B, kinds, kw = "MiniGrid-FourRooms-v0", 96, ("lib", "lib"), {"gamma": 0.5, "tol": 1e-3}
+    cells = gen.generate(env_id, 0, B, enc=False, cells=True, agent=False)["cells"]
+    o = oracle.value_iteration(0, cells, dtype="f32", nthreads=8, **kw)
+    own = [oracle.value_iteration(0, c, dtype="f32", **kw)["dv"] for c in cells]
+    assert o["sweeps"] == 11 and o["dv"] == 2.0 ** -10 and max(own[:48]) > 0 and max(own[48:]) > 0
+    out = mp.Manager().dict()
+    mp.spawn(_multi_worker, args=(2, _port(), env_id, B, "f32", None, kinds, out, kw), nprocs=2, join=True)
+    got = dict(out)
+    assert sorted(got) == [0, 1]
+    for rank, (res, V, pi, lo, hi, ckind) in got.items():
+        assert ckind == "host"
+        for k, nred, nwait, proto in res:
+            assert k == o["sweeps"] and proto == "lib"
+            assert nred >= 2  # {K, E}, then dV(K): the branch only slip reached
+        np.testing.assert_array_equal(V, o["V"][lo:hi])
+        np.testing.assert_array_equal(pi, o["pi"][lo:hi])
