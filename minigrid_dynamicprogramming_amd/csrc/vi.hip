@@ -288,6 +288,7 @@ using N1to8 = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;  // wave2, ban
 using NWave = std::integer_sequence<int, 1, 2, 4, 8>;              // lone wave: cells per lane
 using NMix = std::integer_sequence<int, 2, 3, 4, 5, 6>;            // mix (fp32)
 using NWave2n = std::integer_sequence<int, 2, 3, 4>;               // wave2n: blocks per wave
+using NPairPlane = std::integer_sequence<int, 3, 4, 5>;            // serve_pair: plane stride / 64 (65..256 cells, W 9..16)
 
 template <typename T, int MODEL, bool SLIP, int MAP>
 struct Kernels {
@@ -330,7 +331,10 @@ int resolve_kernels(const ViPlan &p, ViKernels *out) {
             if constexpr (std::is_same<T, float>::value)
                 if (p.kern == Loop::mix) fused(pick<KS::template Fused, Loop::mix>(p.n, f, NMix{}));
             if (p.serve_kern == Loop::serve_ew) serve(KS::template Serve<Loop::serve_ew, 0>::fn);
-            if (p.serve_kern == Loop::serve_pair) serve(KS::template Serve<Loop::serve_pair, 0>::fn);
+            // serve_pair: the plane stride at compile time where the plan names one of these; else at run time
+            if (p.serve_kern == Loop::serve_pair)
+                serve(pick<KS::template Serve, Loop::serve_pair>(p.serve_n, KS::template Serve<Loop::serve_pair, 0>::fn,
+                                                                 NPairPlane{}));
             if (p.serve_kern == Loop::band) serve(pick<KS::template Serve, Loop::band>(p.serve_n, s, N1to8{}));
             if (p.wants_bserve) {  // the wave2 loop of the same P (the capacity of both is the same by bserve_min_waves)
                 b = pick<KS::template BServe, Loop::wave2>(p.wave2, b, N1to8{});

@@ -81,7 +81,8 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
                                            double *__restrict__ dvenv, unsigned long long *__restrict__ host_out,
                                            int k_target, int fresh, bool lone, unsigned int epoch, int e,
                                            int &k, double &dvl, const typename TopoOf<T, MODEL>::type *pre = nullptr,
-                                           unsigned long long *gk = nullptr, int ew = 0) {
+                                           unsigned long long *gk = nullptr, int ew = 0,
+                                           const ServePairTopo<T> *sp = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Smem LY = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
     T *V0 = reinterpret_cast<T *>(smem);
@@ -280,8 +281,14 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         if (k == 0) zero16(V0, geo.S * (int)sizeof(T));
         else copy16(V0, V + vb, geo.S * (int)sizeof(T));
     }
-    if (threadIdx.x < 64) flags[threadIdx.x] = 0;
-    __syncthreads();
+    // the served pair loop's fresh start needs no stage here: it clears its flag bytes once per grid and
+    // sets its first pair's in its own first stage (fused_serve_pair)
+    bool own_start = false;
+    if constexpr (L == Loop::serve_pair) own_start = ew != 0 && k == 0;
+    if (!own_start) {
+        if (threadIdx.x < 64) flags[threadIdx.x] = 0;
+        __syncthreads();
+    }
 
     int cur = 0, parity = 0;
     T diff = (T)0;
@@ -333,8 +340,10 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
             bool ran = false;
             if constexpr (L == Loop::serve_pair) {
                 if (ew) {
-                    fused_serve_pair<T>(geo, cf, V0, V0 + serve_pair_tile_elems(geo.HWs, geo.W), slots, flags,
-                                        V + vb, V + vb, pi + vb, k, dvl, done, *pre, ew == 2);
+                    // N > 0: the plane stride 64 * N at compile time (the plan's serve_n), a tile = 4 planes
+                    const int te = N > 0 ? 4 * 64 * N : serve_pair_tile_elems(geo.HWs, geo.W);
+                    fused_serve_pair<T, N>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done,
+                                           *pre, *sp, ew == 2);
                     ran = true;
                 }
             } else if (ew) {
@@ -540,6 +549,7 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
     __syncthreads();
     // the grid stays put between kServeNewCells requests: resolve this thread's cell topology once
     typename TopoOf<T, MODEL>::type topo;
+    ServePairTopo<T> sp = {};  // Loop::serve_pair: its own per-grid constants
     int ew = 0;  // Loop::serve_ew: 0 = the grid falls back, 1 = fused_serve_xyd, 2 = the same, tiles to clear
     __shared__ int s_ew;
     auto resolve = [&]() {
@@ -548,7 +558,7 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
             if constexpr (MODEL == MGDP_MODEL_XYD) topo = xyd_topo_soa<T>(cl, geo, cc);
             else topo = dk_topo_soa(cl, geo, cc);
         }
-        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) topo.halo = serve_pair_halo(cl, geo, (int)threadIdx.x);
+        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) sp = serve_pair_topo<T>(cl, geo, cf, topo, (int)threadIdx.x);
         if constexpr (loop_is_serve_ew(L)) ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
     };
     resolve();
@@ -613,7 +623,8 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
         double dvl;
         if (!fused_grid<T, MODEL, SLIP, MAP, true, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, -1, 1, true,
                                                    (unsigned int)cmd, 0, k, dvl,
-                                                   (L == Loop::generic || loop_is_serve_ew(L)) ? &topo : nullptr, nullptr, ew) &&
+                                                   (L == Loop::generic || loop_is_serve_ew(L)) ? &topo : nullptr, nullptr, ew,
+                                                   &sp) &&
             threadIdx.x == 0)
             publish_tagged(host_out, k, dvl, (unsigned int)cmd);
         if (ew == 2) ew = 1;  // the tiles' pads stay +0 until the next grid

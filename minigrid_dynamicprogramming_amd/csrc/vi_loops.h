@@ -587,7 +587,8 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
 //    south fronts are the last pair's two neighbour values).  So the rule, the cap (a pair may
 //    compute past it: discarded), the reported dV (the block max of the stopping sweep's |dV|) and
 //    pi (argmax on V_{K-1}, lowest index on ties) are fused_serve_xyd's, bit for bit.
-//  * The solve's first call computes one sweep (its first half is the identity), so the pairs cover
+//  * The solve's first call computes one sweep (its first half is the identity; a solve from V_0 = 0,
+//    which every served request is, makes that sweep in registers instead: `fresh` below), so the pairs cover
 //    sweeps (k_start + 2, k_start + 3), ...: a stop on a pair's second sweep costs the next pair's
 //    first-sweep arithmetic only, a stop on its first sweep that and the pair's second sweep
 //    (Empty-16's 29 sweeps from 0 end on a second sweep).
@@ -608,26 +609,53 @@ __device__ __forceinline__ uint32_t serve_pair_halo(const uint8_t *cl, const Geo
     return h;
 }
 
-template <typename T, typename Done>
+// What the pair loop keeps of thread t's cells besides its XydTopo, resolved once per grid by the
+// server: the discount of its own cell (0 if absorbing) and, for cell t + W (S) and
+// t - W (N), the discount and the goal reward of the plane this thread computes for them.
+template <typename T>
+struct ServePairTopo {
+    T ge, geS, tqS, geN, tqN;
+    int block;  // the workgroup's threads, read from the dispatch packet here and not once per request
+};
+template <typename T>
+__device__ __forceinline__ ServePairTopo<T> serve_pair_topo(const uint8_t *cl, const Geo &geo, const Coef<T> &cf,
+                                                            const XydTopo<T> &tp, int t) {
+    ServePairTopo<T> s;
+    const uint32_t halo = serve_pair_halo(cl, geo, t);
+    s.ge = tp.valid ? cf.g : (T)0;
+    s.geS = (halo & 1u) ? cf.g : (T)0, s.tqS = (halo & 2u) ? (T)1 : (T)0;
+    s.geN = (halo & 4u) ? cf.g : (T)0, s.tqN = (halo & 8u) ? (T)1 : (T)0;
+    s.block = (int)blockDim.x;
+    asm volatile("" : "+s"(s.block));  // an SGPR from here on: the load is not repeated where it is used
+    return s;
+}
+
+// NPL > 0: the plane stride is 64 * NPL elements, known at compile time (the plan's serve_n), so every
+// plane of a cell is an immediate offset from one address register; 0: serve_pair_plane at run time.
+template <typename T, int NPL, typename Done>
 __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &cf, T *T0, T *T1, T *slots,
                                                  uint8_t *flags, const T *Vg, T *Vg_out, int8_t *pig, int &k,
                                                  double &dvl, const Done &done, const XydTopo<T> &tp,
-                                                 bool zero_tiles) {
+                                                 const ServePairTopo<T> &sp, bool zero_tiles) {
     const int c = threadIdx.x, lane = c & 63;
     const int cc = c < geo.HW ? c : 0;
     const bool own_cell = c < geo.HW;
-    const int W = geo.W, PL = serve_pair_plane(geo.HWs, W);
+    const int W = geo.W, PL = NPL > 0 ? 64 * NPL : serve_pair_plane(geo.HWs, W);
     k = __builtin_amdgcn_readfirstlane(k);  // uniform: the sweep count in an SGPR
     const int o0 = serve_pair_pad(W) + c;  // plane d of this cell at d * PL + o0
-    const T ge = tp.valid ? cf.g : (T)0;
+    const T ge = sp.ge;
     T tq[4];  // the goal rewards in registers for the loop (the server's topology may live in memory)
 #pragma unroll
     for (int d = 0; d < 4; ++d) tq[d] = tp.tq[d];
     // the neighbours' topology: cell c + W (its plane 1), cell c - W (its plane 3)
-    const T geS = (tp.halo & 1u) ? cf.g : (T)0, tqS = (tp.halo & 2u) ? (T)1 : (T)0;
-    const T geN = (tp.halo & 4u) ? cf.g : (T)0, tqN = (tp.halo & 8u) ? (T)1 : (T)0;
+    const T geS = sp.geS, tqS = sp.tqS, geN = sp.geN, tqN = sp.tqN;
+    uint8_t *const fwave = flags + (threadIdx.x >> 6);
+    const bool lane0 = lane == 0;
+    // the last pair's |dV| of its two sweeps and its middle set's north / south fronts
+    T dm1p = (T)0, dm2p = (T)0, vSp = (T)0, vNp = (T)0;
     T A[4], B[4], C[4];
-    {
+    const bool fresh = k == 0;  // uniform
+    if (!fresh) {
         V4<T> x = V4<T>{{(T)0, (T)0, (T)0, (T)0}};
         if (k != 0) x = *reinterpret_cast<const V4<T> *>(Vg + cc * 4);
 #pragma unroll
@@ -635,23 +663,49 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     }
     if (zero_tiles) {
         const int te = 4 * PL;
-        for (int i = c; i < te; i += blockDim.x) {  // pads (and planes) of both tiles start at +0
+        for (int i = c; i < te; i += sp.block) {  // pads (and planes) of both tiles start at +0
             T0[i] = (T)0;
             T1[i] = (T)0;
         }
+        // the fresh start leaves the flag bytes of waves the workgroup does not have alone: +0 once per grid
+        if (c < 64) flags[c] = 0;
         __syncthreads();
     }
+    if (fresh) {
+        // A solve from V_0 = +0 (every served request): sweep 1 is vmax(ge * (+0), tq) = tq, exactly, and
+        // the two fronts it keeps are +0, so it is made here in registers and the loop starts as
+        // pair(T0, T1, A, B, C, 0, ..half) leaves its sets: A = B = V_0, C = V_1 (a thread without a cell
+        // shadows cell 0, a wall: tq = +0), V_1's planes in tile 1, this wave's flag byte 0 with the half
+        // pair's bits, k = 1.  Tile 0's planes may still hold the previous solve's values: nothing reads
+        // them before pair 0 has written all of them (the stop test cannot end on p = 0 with stop == 1, as
+        // bit 0 is set here); the pads of both tiles stay +0 from the grid's first solve.  The other flag
+        // slot is cleared in the same stage.  One barrier; the caller has none of its own on this path.
+        T dm = (T)0;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        B[d] = (T)0;
-        C[d] = (T)0;
-        T0[d * PL + o0] = A[d];
+        for (int d = 0; d < 4; ++d) {
+            A[d] = (T)0;
+            B[d] = (T)0;
+            C[d] = vmax((T)0, tq[d]);
+            dm = vmax(dm, C[d]);
+            T1[d * PL + o0] = C[d];
+        }
+        const uint32_t bits = 1u | (__ballot(dm >= cf.tol) != 0ull && 1 < geo.max_sweeps ? 2u : 0u);
+        if (lane0) {
+            fwave[0] = (uint8_t)bits;
+            fwave[16] = 0;
+        }
+        dm2p = dm;
+        __syncthreads();
+        k = 1;
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            B[d] = (T)0;
+            C[d] = (T)0;
+            T0[d * PL + o0] = A[d];
+        }
+        __syncthreads();
     }
-    __syncthreads();
-    uint8_t *const fwave = flags + (threadIdx.x >> 6);
-    const bool lane0 = lane == 0;
-    // the last pair's |dV| of its two sweeps and its middle set's north / south fronts
-    T dm1p = (T)0, dm2p = (T)0, vSp = (T)0, vNp = (T)0;
     int stop = 0;  // 1: K = k - 1, 2: K = k
     // one sweep of this lane's cell from its own values and its four geometric fronts (fused_serve_xyd's)
     auto step = [&](const T (&in)[4], const T fE, const T fS, const T fW, const T fN, T (&out)[4]) -> T {
@@ -700,15 +754,19 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
 #pragma unroll
         for (int d = 0; d < 4; ++d) Tout[d * PL + o0] = out[d];
         constexpr int n = HALF ? 1 : 2;  // sweeps this call computes
-        const uint32_t bits = (HALF || (__ballot(dm1 >= cf.tol) != 0ull && k + 1 < geo.max_sweeps) ? 1u : 0u) |
-                              (__ballot(dm2 >= cf.tol) != 0ull && k + n < geo.max_sweeps ? 2u : 0u);
+        // The sweep counts are made ahead of the tests, not inside their short-circuit arms: there the
+        // compiler re-used k + n for the count on one side of lane 0's branch only, and each pair carried a
+        // split exec region with both counts in it (0.4 us per solve).
+        const int k1 = k + 1, kn = k + n;
+        const uint32_t bits = (HALF || (__ballot(dm1 >= cf.tol) != 0ull && k1 < geo.max_sweeps) ? 1u : 0u) |
+                              (__ballot(dm2 >= cf.tol) != 0ull && kn < geo.max_sweeps ? 2u : 0u);
         if (lane0) fwave[par * 16] = (uint8_t)bits;
         dm1p = dm1;
         dm2p = dm2;
         vSp = vS;
         vNp = vN;
         __syncthreads();
-        k += n;
+        k = kn;
         return true;
     };
     using Yes = std::integral_constant<bool, true>;
@@ -717,7 +775,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     // p % 3: (C, B), (B, A), (A, C) -- `in` = V_k, `out` = V_{k-1} (the last pair's middle set) -- and its
     // output tile (T0 for even p) still holds V_{k-2}, the last pair's input.
     int p;
-    pair(T0, T1, A, B, C, 0, No{}, Yes{});
+    if (!fresh) pair(T0, T1, A, B, C, 0, No{}, Yes{});
     while (true) {
         if (!pair(T1, T0, C, A, B, 1, Yes{}, No{})) { p = 0; break; }
         if (!pair(T0, T1, B, C, A, 0, Yes{}, No{})) { p = 1; break; }
@@ -728,7 +786,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     }
     const T diff = stop == 1 ? dm1p : dm2p;
     if (stop == 1) k -= 1;
-    dvl = (double)block_max(diff, slots, 0);
+    dvl = (double)block_max_nw(diff, slots, 0, (int)threadIdx.x, sp.block >> 6);
     done(k, dvl);
     // element selects (a pointer to one of the sets would put them in scratch)
     const int r = p % 3;

@@ -105,16 +105,20 @@ __device__ __forceinline__ int late_tid(int wave_s) {
 // Block-wide max with ONE barrier; slots = [2][16] alternating by parity so that consecutive
 // calls never race (a slot set is rewritten only after every thread passed the next barrier).
 // tid: the caller's thread index (late_tid after a long loop).
+// nw: the workgroup's waves (a caller that holds the block size already passes it)
 template <typename T>
-__device__ __forceinline__ T block_max_tid(T v, T *slots, int parity, int tid) {
+__device__ __forceinline__ T block_max_nw(T v, T *slots, int parity, int tid, int nw) {
     v = wave_max(v);
     const int w = tid >> 6;
     if ((tid & 63) == 0) slots[parity * 16 + w] = v;
     __syncthreads();
-    const int nw = blockDim.x >> 6;
     T m = slots[parity * 16];
     for (int i = 1; i < nw; ++i) m = tmax(m, slots[parity * 16 + i]);
     return m;
+}
+template <typename T>
+__device__ __forceinline__ T block_max_tid(T v, T *slots, int parity, int tid) {
+    return block_max_nw(v, slots, parity, tid, (int)(blockDim.x >> 6));
 }
 template <typename T>
 __device__ __forceinline__ T block_max(T v, T *slots, int parity) { return block_max_tid(v, slots, parity, (int)threadIdx.x); }
@@ -154,7 +158,6 @@ struct XydTopo {
     int nbi[4];      // V index read by forward from dir d (own state when blocked / terminal / invalid)
     T tq[4];         // terminal forward value: 1 (goal, R = 1) or 0 (lava)
     uint32_t lavaF;  // NoDeath: bit d = forward from dir d enters (walkable, non-terminal) lava
-    uint32_t halo;   // served pair loop (serve_pair_halo): bit 0 the halo cell is walkable, bit 1 a goal ahead of it
 };
 
 template <typename T, bool ND = false>
@@ -164,7 +167,6 @@ __device__ __forceinline__ XydTopo<T> xyd_topo(const uint8_t *cl, const Geo &geo
     tp.valid = xyd_free(cl[c]) || (ND && cl[c] == T_LAVA);
     tp.term = 0;
     tp.lavaF = 0;
-    tp.halo = 0;
     // Branch-free (selects only, every LDS byte read unconditional): it runs once per grid-sweep
     // in the HBM sweep kernels.
 #pragma unroll
