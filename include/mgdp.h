@@ -249,6 +249,39 @@ int mgdp_comm_host_waits(const mgdp_comm *comm, int64_t *waits, int32_t *kind);
 int mgdp_vi_solve_sharded(mgdp_vi *vi, mgdp_comm *comm, int32_t *sweeps_out, double *dv_out,
                           int32_t *converged_out);
 
+/* Policy evaluation, improvement and policy iteration (additive entry points,
+ * the ABI version is unchanged).  Fused method, horizon 0, terminal lava (MGDP_E_UNSUPPORTED
+ * otherwise, and for a grid whose two V tiles, cells and packed pi exceed a CU's LDS); slip as the
+ * handle was created.  pi: B*S int8 in the state order and action encoding of mgdp_vi_get_policy
+ * (XYD 0..6; DoorKey lanes 0..4 = left, right, forward, pickup, toggle).  Entries of absorbing
+ * states are ignored and stored as -1; an entry outside [0, A) on a valid state is MGDP_E_INVALID
+ * (the message names the first offending grid and state; detected on the device).
+ *   mgdp_vi_evaluate: V^pi by Jacobi sweeps from V_0 = 0, V_{k+1}[s] = Q_k[s, pi(s)] with the Q of
+ *     the solve (same arithmetic, same order), stopped by the solve's global rule: after the sweep
+ *     whose max|dV| over all grids < tol, or at max_sweeps (converged = 0).  Bit-identical to the
+ *     literal global loop.  Afterwards mgdp_vi_get_values returns V^pi, mgdp_vi_get_policy the
+ *     evaluated policy, mgdp_vi_get_grid_sweeps the per-grid sweeps under the solve's contract, and
+ *     mgdp_vi_kernel_time counts the evaluation's launches.  The handle's protocol state is the
+ *     evaluation's: mgdp_vi_run_local / run_to / sweep / resume (and the *_dev forms) are refused
+ *     until mgdp_vi_reset; mgdp_vi_solve resets and behaves as before.
+ *   mgdp_vi_evaluate_device: the same with the policy in device memory (16-byte aligned, complete
+ *     before the call); NULL evaluates the handle's own pi buffer, e.g. pi* right after a solve.
+ *   mgdp_vi_improve: pi'(s) = argmax_a Q(s, a) on the handle's current V (after a solve or an
+ *     evaluation), written over the handle's pi; the lowest action index wins ties, except that
+ *     pi(s) is kept when Q(s, pi(s)) equals the maximum.  changed_out = valid states whose action
+ *     changed, over the batch.
+ *   mgdp_vi_policy_iteration: pi_0 = pi0 (host, B*S) or "forward" on every valid state (NULL);
+ *     repeat {evaluate from V_0 = 0, improve} until no state changed or max_iters iterations.
+ *     iters_out = iterations run, eval_sweeps_out = their evaluation sweeps summed, changed_out =
+ *     the last improvement's count, dv_out = the last evaluation's dV.  V is the last evaluation's,
+ *     pi the final policy. */
+int mgdp_vi_evaluate(mgdp_vi *vi, const int8_t *pi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out);
+int mgdp_vi_evaluate_device(mgdp_vi *vi, const int8_t *d_pi, int32_t *sweeps_out, double *dv_out,
+                            int32_t *converged_out);
+int mgdp_vi_improve(mgdp_vi *vi, int64_t *changed_out);
+int mgdp_vi_policy_iteration(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
+                             int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out);
+
 /* Results (host).  V: B*S of float or double per dtype; pi: B*S int8 (-1 = absorbing state). */
 int mgdp_vi_get_values(mgdp_vi *vi, void *V);
 int mgdp_vi_get_policy(mgdp_vi *vi, int8_t *pi);

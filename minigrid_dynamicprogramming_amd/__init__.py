@@ -3,6 +3,8 @@
 Hot path (HIP, gfx950, libmgdp.so behind include/mgdp.h):
   * MiniGridEnv.step / gen_obs for batches of envs            (csrc/envs.hip)
   * Jacobi value iteration over (pos, dir[, has_key, door_open]) (csrc/vi.hip)
+  * policy evaluation (V^pi of a given policy), greedy improvement and policy iteration on the
+    same model and stopping rule                              (csrc/vi_eval.h)
 Host side (this package): the reference's env API, registry and grid generators, the DP front end
 and the multi-GPU driver.  See DESIGN.md.
 """
@@ -11,7 +13,7 @@ from .core import (COLOR_NAMES, COLOR_TO_IDX, DIR_TO_VEC, IDX_TO_COLOR, IDX_TO_O
 from .minigrid_env import MiniGridEnv, MissionSpace
 from .envs import CrossingEnv, DistShiftEnv, DoorKeyEnv, EmptyEnv, FourRoomsEnv, LavaGapEnv
 from .registry import EnvSpec, make, register, registry
-from .dp import ValueIteration, VIResult, value_iteration
+from .dp import ValueIteration, VIResult, policy_evaluation, policy_iteration, value_iteration
 from .vector import MiniGridVecEnv
 
 __version__ = "0.1.0"

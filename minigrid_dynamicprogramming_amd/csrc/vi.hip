@@ -23,6 +23,8 @@
 //   vi_fused_opts_kernel  the fused solve with NoDeath lava / finite horizon.
 //   vi_sweep_kernel   one Jacobi sweep of every grid: per grid, V'[grid] is staged HBM->LDS (the
 //                     LDS tile of the neighbourhood), updated from LDS, written back.
+//   vi_eval_kernel / vi_improve_kernel (vi_eval.h)  policy evaluation under the same protocol, and the
+//                     greedy improvement step.
 // Device code is split into vi_model.h (model), vi_loops.h (workgroup loops), vi_kernels.h
 // (kernels); this file holds the host side and the C ABI.  Which loop a handle runs is decided once,
 // in vi_plan.h (host-plain: plan_vi); vi_layout.h holds the LDS sizes host and device share.
@@ -50,6 +52,7 @@
 #include "vi_model.h"
 #include "vi_loops.h"
 #include "vi_kernels.h"
+#include "vi_eval.h"
 
 
 // ================================================================================================
@@ -137,6 +140,10 @@ struct mgdp_vi {
     unsigned long long *d_gk = nullptr;    // the in-launch reduction's device words (GkCtx; plan.gk)
     unsigned long long *d_breq = nullptr;  // the resident batch server's device words (kBreqWords): forwarded request, exit counter
     bool solving = false;                // inside mgdp_vi_solve: its run_local may use the batch server
+    // policy evaluation / improvement (vi_eval.h): {policy error word, changed-state count}, allocated
+    // at the first evaluation; `evaluated`: kenv / dvenv / V are an evaluation's (cleared by mgdp_vi_reset)
+    unsigned long long *d_eval = nullptr;
+    bool evaluated = false;
 };
 
 namespace {
@@ -957,6 +964,7 @@ int mgdp_vi_destroy(mgdp_vi *vi) {
     (void)hipFree(vi->d_breq);
     (void)hipFree(vi->d_rgoal);
     (void)hipFree(vi->d_pi_t);
+    (void)hipFree(vi->d_eval);
     if (vi->h_out) (void)hipHostFree(vi->h_out);
     if (vi->h_stage) (void)hipHostFree(vi->h_stage);
     if (vi->own_stream) (void)hipStreamDestroy(vi->stream);
@@ -1112,12 +1120,14 @@ int mgdp_vi_reset(mgdp_vi *vi) {
     vi->k_done_valid = false;
     vi->sweeps = 0;
     vi->converged = 0;
+    vi->evaluated = false;
     return 0;
 }
 
 int mgdp_vi_run_local(mgdp_vi *vi, int32_t *k_local_max) {
     MGDP_CHECK(vi && k_local_max, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     DeviceGuard guard(vi->d.device);
     if (vi->d.method == MGDP_METHOD_FUSED) {
         // the batch server only for mgdp_vi_solve's own run_local: a caller driving run_local / run_to
@@ -1150,6 +1160,7 @@ int mgdp_vi_run_local(mgdp_vi *vi, int32_t *k_local_max) {
 int mgdp_vi_run_to(mgdp_vi *vi, int32_t k_target, double *dv_out) {
     MGDP_CHECK(vi && dv_out, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(k_target >= 0 && k_target <= vi->d.max_sweeps, MGDP_E_INVALID, "k_target %d out of range", k_target);
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     DeviceGuard guard(vi->d.device);
     if (vi->d.method == MGDP_METHOD_FUSED) {
         // every grid is already there: at k_target, or every grid at an exact fixed point (the
@@ -1202,6 +1213,7 @@ int mgdp_vi_run_to_dev(mgdp_vi *vi, const int64_t *d_k, int64_t *d_pub) {
     MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the device protocol runs the fused method without horizon / lava options");
     MGDP_CHECK(!vi->fresh, MGDP_E_INVALID, "mgdp_vi_run_to_dev before mgdp_vi_run_local_dev");
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     DeviceGuard guard(vi->d.device);
     vi->k_done_valid = false;
     return launch_fused(vi, 0, reinterpret_cast<unsigned long long *>(d_pub), reinterpret_cast<const long long *>(d_k));
@@ -1212,6 +1224,7 @@ int mgdp_vi_run_to_dev_sync(mgdp_vi *vi, const int64_t *d_kdv, int32_t *k_out, d
     MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && !vi->plan.opts, MGDP_E_UNSUPPORTED,
                "the device protocol runs the fused method without horizon / lava options");
     MGDP_CHECK(!vi->fresh, MGDP_E_INVALID, "mgdp_vi_run_to_dev_sync before mgdp_vi_run_local_dev");
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     DeviceGuard guard(vi->d.device);
     vi->k_done_valid = false;
     int32_t km = 0;
@@ -1275,6 +1288,7 @@ int mgdp_vi_set_result(mgdp_vi *vi, int32_t k, double dv) {
 
 int mgdp_vi_sweep(mgdp_vi *vi, double *dv_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     if (vi->d.method == MGDP_METHOD_FUSED) {
         MGDP_CHECK(vi->k_done_valid && vi->k_min == vi->k_max, MGDP_E_INVALID,
                    "mgdp_vi_sweep: grids are not at a common sweep index (call mgdp_vi_run_to first)");
@@ -1456,6 +1470,7 @@ int mgdp_vi_resume(mgdp_vi *vi, const void *V, int32_t k, double dv, int32_t *sw
                    int32_t *converged_out) {
     MGDP_CHECK(vi && V, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
+    MGDP_CHECK(!vi->evaluated, MGDP_E_INVALID, "the handle holds a policy evaluation: call mgdp_vi_reset first");
     MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0, MGDP_E_INVALID,
                "resume: the fused method with an infinite horizon");
     MGDP_CHECK(k >= 1 && k < vi->d.max_sweeps, MGDP_E_INVALID, "resume: sweep %d outside [1, max_sweeps)", k);
@@ -1493,6 +1508,203 @@ int mgdp_vi_resume(mgdp_vi *vi, const void *V, int32_t k, double dv, int32_t *sw
     if (sweeps_out) *sweeps_out = K;
     if (dv_out) *dv_out = dv2;
     if (converged_out) *converged_out = vi->converged;
+    return 0;
+}
+
+// Policy evaluation, improvement and policy iteration (kernels in vi_eval.h).
+// An evaluation is the solve's protocol on vi_eval_kernel: every grid to its own stop, the grids that
+// stopped with dV != 0 to K = max k_e, then the global rule sweep by sweep if dV(K) >= tol.
+extern "C++" {  // the launch helpers are templates
+namespace {
+int eval_supported(const mgdp_vi *vi, const char *what) {
+    MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED, MGDP_E_UNSUPPORTED, "%s runs on the fused method only", what);
+    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED, "%s is defined for the discounted problem (horizon 0)", what);
+    MGDP_CHECK(vi->d.lava_mode == MGDP_LAVA_TERMINAL, MGDP_E_UNSUPPORTED,
+               "%s needs terminal lava (NoDeath makes V negative)", what);
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    MGDP_CHECK(s.lds <= 160 * 1024, MGDP_E_UNSUPPORTED,
+               "%s: grid too large for the LDS-resident evaluation (%d B > 160 KiB)", what, s.lds);
+    return 0;
+}
+
+Geo eval_geo(const mgdp_vi *vi, const EvalShape &s) {
+    Geo g = make_geo(vi);
+    g.HWs = s.HWs;
+    g.Ss = s.Ss;
+    g.nbuf = 2;
+    g.quad = g.pair = g.nmix = g.wt = 0;
+    g.order = nullptr;
+    g.kprio[0] = g.kprio[1] = g.kprio[2] = 0;
+    return g;
+}
+
+int eval_buffers(mgdp_vi *vi) {
+    if (!vi->d_eval) MGDP_HIP(hipMalloc((void **)&vi->d_eval, 2 * sizeof(unsigned long long)));
+    return 0;
+}
+
+template <typename T, int MODEL, bool SLIP>
+int launch_eval_t(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    auto kern = vi_eval_kernel<T, MODEL, SLIP>;
+    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
+    TimedPair tp;
+    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
+                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
+                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, k_target, vi->fresh,
+                          vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
+    MGDP_HIP(hipGetLastError());
+    vi->fresh = 0;
+    if (vi->d.B > vi->kn.inkernel_max) {
+        launch_reduce(vi, vi->d_hout);
+        MGDP_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+template <typename T, int MODEL, bool SLIP>
+int launch_improve_t(mgdp_vi *vi) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    auto kern = vi_improve_kernel<T, MODEL, SLIP>;
+    if (s.improve_lds > 64 * 1024)
+        MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.improve_lds));
+    hipLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.improve_block), s.improve_lds, vi->stream, eval_geo(vi, s),
+                       make_coef<T>(vi), vi->d_cells, (const T *)vi->d_V[0], vi->d_pi, vi->d_eval + 1);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+// dispatch on (dtype, model, slip); the mapping does not apply (one thread per cell)
+template <typename T>
+int launch_eval_m(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_eval_t<T, MGDP_MODEL_DOORKEY, false>(vi, k_target, pi_src);
+    return vi->d.slip_p >= 0.0 ? launch_eval_t<T, MGDP_MODEL_XYD, true>(vi, k_target, pi_src)
+                               : launch_eval_t<T, MGDP_MODEL_XYD, false>(vi, k_target, pi_src);
+}
+int launch_eval(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    return vi->d.dtype == MGDP_F32 ? launch_eval_m<float>(vi, k_target, pi_src) : launch_eval_m<double>(vi, k_target, pi_src);
+}
+template <typename T>
+int launch_improve_m(mgdp_vi *vi) {
+    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_improve_t<T, MGDP_MODEL_DOORKEY, false>(vi);
+    return vi->d.slip_p >= 0.0 ? launch_improve_t<T, MGDP_MODEL_XYD, true>(vi) : launch_improve_t<T, MGDP_MODEL_XYD, false>(vi);
+}
+
+// The evaluation of the policy at d_src (device; the handle's own buffer included), stream idle of
+// servers.  The dispatch order a later solve would learn from the previous solve's executed sweeps is
+// learned first: the evaluation overwrites d_kexec with its own and must not feed that order.
+int eval_run(mgdp_vi *vi, const int8_t *d_src, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
+    if (!vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi))
+        if (int rc = learn_dispatch(vi)) return rc;
+    if (int rc = eval_buffers(vi)) return rc;
+    MGDP_HIP(hipMemsetAsync(vi->d_eval, 0xff, sizeof(unsigned long long), vi->stream));
+    vi->fresh = 1;
+    vi->cur = 0;
+    vi->k_done = vi->k_min = 0;
+    vi->k_done_valid = false;
+    vi->sweeps = vi->converged = 0;
+    vi->evaluated = true;  // whatever follows, kenv / dvenv / V are no longer a solve's
+    int32_t k = 0, km = 0;
+    double dv = 0.0;
+    if (int rc = launch_eval(vi, -1, d_src)) return rc;
+    if (int rc = reduce_env(vi, &k, &dv)) return rc;
+    unsigned long long err = kEvalNoError;
+    MGDP_HIP(hipMemcpyAsync(&err, vi->d_eval, sizeof(err), hipMemcpyDeviceToHost, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));
+    vi->k_done_valid = false;
+    MGDP_CHECK(err == kEvalNoError, MGDP_E_INVALID, "policy: grid %d state %d: action %d is outside [0, %d)",
+               (int)(err >> 32), (int)((err >> 8) & 0xffffffu), (int)(int8_t)(err & 0xffu), vi->A);
+    // run_to(K): nothing to launch when every grid is at K or at an exact fixed point (mgdp_vi_run_to)
+    if (!(vi->k_min == k || (vi->dv_red == 0.0 && vi->k_min > 0))) {
+        if (int rc = launch_eval(vi, k, nullptr)) return rc;
+        if (int rc = reduce_env(vi, &km, &dv)) return rc;
+        MGDP_CHECK(km == k, MGDP_E_INVALID, "evaluate: run_to(%d) ended at sweep %d", k, km);
+    }
+    while (!(dv < vi->d.tol) && k < vi->d.max_sweeps) {  // contraction broken by rounding: global rule
+        if (int rc = launch_eval(vi, k + 1, nullptr)) return rc;
+        if (int rc = reduce_env(vi, &km, &dv)) return rc;
+        ++k;
+    }
+    vi->k_done = k;
+    vi->k_done_valid = false;  // the protocol entry points need a reset after an evaluation
+    vi->sweeps = k;
+    vi->converged = dv < vi->d.tol;
+    if (sweeps_out) *sweeps_out = k;
+    if (dv_out) *dv_out = dv;
+    if (converged_out) *converged_out = vi->converged;
+    return 0;
+}
+
+int improve_run(mgdp_vi *vi, int64_t *changed_out) {
+    if (int rc = eval_buffers(vi)) return rc;
+    MGDP_HIP(hipMemsetAsync(vi->d_eval + 1, 0, sizeof(unsigned long long), vi->stream));
+    if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_m<float>(vi) : launch_improve_m<double>(vi)) return rc;
+    unsigned long long n = 0;
+    MGDP_HIP(hipMemcpyAsync(&n, vi->d_eval + 1, sizeof(n), hipMemcpyDeviceToHost, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));
+    if (changed_out) *changed_out = (int64_t)n;
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mgdp_vi_evaluate_device(mgdp_vi *vi, const int8_t *d_pi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    if (int rc = eval_supported(vi, "policy evaluation")) return rc;
+    MGDP_CHECK(((uintptr_t)d_pi & 15u) == 0, MGDP_E_INVALID, "policy: the device pointer must be 16-byte aligned");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    return eval_run(vi, d_pi ? d_pi : vi->d_pi, sweeps_out, dv_out, converged_out);
+}
+
+int mgdp_vi_evaluate(mgdp_vi *vi, const int8_t *pi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
+    MGDP_CHECK(vi && pi, MGDP_E_INVALID, "null argument");
+    if (int rc = eval_supported(vi, "policy evaluation")) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi, (size_t)vi->d.B * vi->S, hipMemcpyHostToDevice, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));  // the caller's buffer is free when this returns
+    return eval_run(vi, vi->d_pi, sweeps_out, dv_out, converged_out);
+}
+
+int mgdp_vi_improve(mgdp_vi *vi, int64_t *changed_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    if (int rc = eval_supported(vi, "policy improvement")) return rc;
+    MGDP_CHECK(vi->sweeps > 0, MGDP_E_INVALID, "policy improvement: no value function (solve or evaluate first)");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    return improve_run(vi, changed_out);
+}
+
+int mgdp_vi_policy_iteration(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
+                             int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(max_iters > 0, MGDP_E_INVALID, "max_iters must be > 0");
+    if (int rc = eval_supported(vi, "policy iteration")) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    const size_t BS = (size_t)vi->d.B * vi->S;
+    if (pi0) {
+        MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi0, BS, hipMemcpyHostToDevice, vi->stream));
+        MGDP_HIP(hipStreamSynchronize(vi->stream));
+    } else {  // "forward" everywhere; the evaluation stores -1 on absorbing states
+        MGDP_HIP(hipMemsetAsync(vi->d_pi, 2, BS, vi->stream));
+    }
+    int32_t iters = 0, k = 0;
+    int64_t total = 0, changed = 0;
+    double dv = 0.0;
+    do {
+        if (int rc = eval_run(vi, vi->d_pi, &k, &dv, nullptr)) return rc;
+        if (int rc = improve_run(vi, &changed)) return rc;
+        total += k;
+        ++iters;
+    } while (changed != 0 && iters < max_iters);
+    if (iters_out) *iters_out = iters;
+    if (eval_sweeps_out) *eval_sweeps_out = total;
+    if (changed_out) *changed_out = changed;
+    if (dv_out) *dv_out = dv;
     return 0;
 }
 

@@ -101,6 +101,11 @@ class VIResult:
     model: str
     W: int
     H: int
+    # policy_iteration() only: improvement iterations, their evaluation sweeps summed, and the states the
+    # last improvement changed (0: the policy is stable); `sweeps` is then the last evaluation's count
+    iters: int | None = None
+    eval_sweeps: int | None = None
+    changed: int | None = None
 
     def value(self, b: int, x: int, y: int, d: int, has_key: int = 0, door_open: int = 0):
         return self.V[b, state_index(self.model, self.W, x, y, d, has_key, door_open)]
@@ -276,6 +281,70 @@ class ValueIteration:
         # measurable part of the host's turnaround between requests
         self._live = self._out
         return self._out[0].value
+
+    # -- policy evaluation / improvement / policy iteration
+    def _check_policy(self, pi) -> np.ndarray:
+        """(B, S) int8 action lanes (any integer dtype that fits), checked before any device work."""
+        a = np.asarray(pi)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
+        if a.shape != (self.B, self.S):
+            raise ValueError(f"policy of shape {a.shape} does not match the handle's {(self.B, self.S)}")
+        if a.dtype != np.int8:
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError("policy entries do not fit int8 action lanes")
+            a = a.astype(np.int8)
+        return np.ascontiguousarray(a)
+
+    def evaluate(self, pi) -> int:
+        """V^pi of a policy (mgdp_vi_evaluate): pi is (B, S) int8 in policy()'s state order and action
+        lanes; entries of absorbing states are ignored (stored as -1), an entry outside [0, A) on a
+        valid state raises ValueError naming grid and state.  Returns the sweeps of the global
+        stopping rule; values(), policy(), grid_sweeps() and result() then describe the evaluation.
+        run_to / sweep / resume need a reset() afterwards; solve() works as before."""
+        a = self._check_policy(pi)
+        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
+        _lib.check(self.L.mgdp_vi_evaluate(self.h, _lib.ptr(a), ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
+                   "mgdp_vi_evaluate")
+        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
+        return self.sweeps
+
+    def evaluate_device(self, pi_ptr: int | None = None) -> int:
+        """evaluate() of a policy in device memory (mgdp_vi_evaluate_device): B*S int8 at `pi_ptr`
+        (16-byte aligned, e.g. a torch int8 tensor's data_ptr()); None evaluates the handle's own pi
+        buffer -- pi* right after a solve()."""
+        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
+        _lib.check(self.L.mgdp_vi_evaluate_device(self.h, None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)),
+                                                  ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
+                   "mgdp_vi_evaluate_device")
+        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
+        return self.sweeps
+
+    def improve(self) -> int:
+        """Greedy improvement on the handle's V (mgdp_vi_improve): pi(s) <- argmax_a Q(s, a), lowest
+        index among ties except that the current action stays when it attains the maximum.  Returns
+        the number of states whose action changed, over the batch."""
+        n = ctypes.c_int64(0)
+        _lib.check(self.L.mgdp_vi_improve(self.h, ctypes.byref(n)), "mgdp_vi_improve")
+        return n.value
+
+    def policy_iteration(self, pi0=None, max_iters: int = 1000) -> dict:
+        """Policy iteration (mgdp_vi_policy_iteration) from pi0 ((B, S) int8; None: "forward" on every
+        valid state): evaluate from V_0 = 0, improve, until no state changes or max_iters.  Returns
+        dict(iters, eval_sweeps, changed, dv); values() is the last evaluation's V, policy() the final pi."""
+        a = None if pi0 is None else self._check_policy(pi0)
+        if int(max_iters) <= 0:
+            raise ValueError("max_iters must be > 0")
+        it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
+        _lib.check(self.L.mgdp_vi_policy_iteration(self.h, None if a is None else _lib.ptr(a), int(max_iters),
+                                                   ctypes.byref(it), ctypes.byref(tot), ctypes.byref(ch), ctypes.byref(dv)),
+                   "mgdp_vi_policy_iteration")
+        # converged of the last evaluation: dv < tol unless max_sweeps capped it
+        self.dv = dv.value
+        self.converged = dv.value < self.tol
+        # the last evaluation's K is the largest per-grid count (a grid below K ended at a fixed point)
+        self.sweeps = int(self.grid_sweeps().max())
+        return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
 
     # sweeps / dv / converged of the last result: read from solve()'s outputs while they are current
     def _result_attr(self, i, name):
@@ -518,6 +587,30 @@ class ValueIteration:
     @property
     def updates_per_sweep(self) -> int:
         return self.B * self.S * n_actions(self.model)
+
+
+def policy_evaluation(grids, pi, **kwargs) -> VIResult:
+    """V^pi of one policy per grid ((B, S) int8, see ValueIteration.evaluate) on one GPU; kwargs as
+    ValueIteration (gamma, tol, slip_p, dtype, ...).  The result's pi is the evaluated policy."""
+    vi = ValueIteration(grids, **kwargs)
+    try:
+        vi.evaluate(pi)
+        return vi.result()
+    finally:
+        vi.close()
+
+
+def policy_iteration(grids, pi0=None, max_iters: int = 1000, **kwargs) -> VIResult:
+    """Policy iteration on one GPU (ValueIteration.policy_iteration); the result carries iters,
+    eval_sweeps and changed, and its sweeps is the last evaluation's count."""
+    vi = ValueIteration(grids, **kwargs)
+    try:
+        r = vi.policy_iteration(pi0, max_iters=max_iters)
+        out = vi.result()
+        out.iters, out.eval_sweeps, out.changed = r["iters"], r["eval_sweeps"], r["changed"]
+        return out
+    finally:
+        vi.close()
 
 
 def value_iteration(grids, **kwargs) -> VIResult:

@@ -1,0 +1,123 @@
+"""Policy evaluation / policy iteration: facts of the numpy restatement (tests/policy_ref.py) that the
+GPU tests build on, and the C ABI of the new entry points.  No GPU.
+
+The restatement is checked against the oracle where the two must meet: evaluating the oracle's pi* of a
+deterministic batch reproduces the oracle's value iteration bit for bit (V_k^{pi*} = V_k on every
+sweep: the greedy action of V_{k-1} stays greedy), and policy iteration ends at V*.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import minigrid_dynamicprogramming_amd as mg
+from minigrid_dynamicprogramming_amd import _lib
+from oracle import oracle
+from tests.policy_ref import PolicyRef
+
+NEW_SYMBOLS = ("mgdp_vi_evaluate", "mgdp_vi_evaluate_device", "mgdp_vi_improve", "mgdp_vi_policy_iteration")
+
+
+@functools.lru_cache(maxsize=None)
+def fourrooms():
+    env = mg.make("MiniGrid-FourRooms-v0")
+    return np.stack([env.generate(seed=s)[0][..., 0].T for s in range(4)]).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def doorkey8():
+    env = mg.make("MiniGrid-DoorKey-8x8-v0")
+    return np.stack([env.generate(seed=s)[0][..., 0].T for s in range(4)]).astype(np.uint8)
+
+
+def test_abi_exports_the_policy_entry_points():
+    L = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(L, name), name
+    assert L.mgdp_abi_version() == 12  # additive: the version does not move
+    # argument validation before any device work
+    assert L.mgdp_vi_evaluate(None, None, None, None, None) == _lib.MGDP_E_INVALID
+    assert L.mgdp_vi_improve(None, None) == _lib.MGDP_E_INVALID
+    assert L.mgdp_vi_policy_iteration(None, None, 1, None, None, None, None) == _lib.MGDP_E_INVALID
+    assert {"policy_evaluation", "policy_iteration"} <= set(dir(mg))
+    for m in ("evaluate", "evaluate_device", "improve", "policy_iteration"):
+        assert callable(getattr(mg.ValueIteration, m))
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("model,grids,sweeps", [(0, fourrooms, 32), (1, doorkey8, 24)])
+def test_deterministic_evaluation_of_pi_star_reproduces_vi(model, grids, sweeps, dtype):
+    cells = grids()
+    o = oracle.value_iteration(model, cells, dtype=dtype, fixed_point=True)
+    assert o["sweeps"] == sweeps
+    r = PolicyRef(model, cells, dtype=dtype).evaluate(o["pi"])
+    assert r["sweeps"] == sweeps and r["dv"] == o["dv"] and r["converged"]
+    np.testing.assert_array_equal(r["V"], o["V"])
+    np.testing.assert_array_equal(r["pi"], o["pi"])
+    np.testing.assert_array_equal(r["grid_sweeps"], o["grid_sweeps"])
+
+
+def test_long_slip_evaluations_stay_under_the_cap():
+    ref = PolicyRef(0, fourrooms(), slip_p=0.5, dtype="f32")
+    for a in range(7):
+        r = ref.evaluate(np.full((4, ref.S), a, np.int8))
+        assert 615 <= r["sweeps"] <= 618, (a, r["sweeps"])
+        assert 0.0 < r["dv"] < 1e-6 and r["converged"]
+        # no grid is at an exact fixed point: every grid is taken to the global K
+        np.testing.assert_array_equal(r["grid_sweeps"], np.full(4, r["sweeps"], np.int32))
+
+
+def test_invalid_lane_is_refused_and_absorbing_lanes_are_ignored():
+    ref = PolicyRef(0, fourrooms()[:1], dtype="f32")
+    pi = np.full((1, ref.S), 2, np.int8)
+    pi[ref.absorb] = 7
+    assert (ref.normalise(pi)[ref.absorb] == -1).all()
+    s = int(np.nonzero(~ref.absorb[0])[0][5])
+    pi[0, s] = 7
+    with pytest.raises(ValueError, match=f"grid 0 state {s}"):
+        ref.normalise(pi)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_policy_iteration_fourrooms_reaches_v_star(dtype):
+    cells = fourrooms()
+    o = oracle.value_iteration(0, cells, dtype=dtype)
+    r = PolicyRef(0, cells, dtype=dtype).policy_iteration()
+    assert r["iters"] == 11 and r["changed"] == 0 and r["changes"][-1] == 0 and all(c > 0 for c in r["changes"][:-1])
+    np.testing.assert_array_equal(r["V"], o["V"])
+
+
+def test_policy_iteration_doorkey_reaches_v_star():
+    cells = doorkey8()
+    o = oracle.value_iteration(1, cells, dtype="f32")
+    r = PolicyRef(1, cells, dtype="f32").policy_iteration()
+    assert r["iters"] == 12 and r["changed"] == 0
+    np.testing.assert_array_equal(r["V"], o["V"])
+
+
+def test_policy_iteration_slip_from_all_done():
+    cells = fourrooms()
+    ref = PolicyRef(0, cells, slip_p=0.9, dtype="f64")
+    r = ref.policy_iteration(np.full((4, ref.S), 6, np.int8))
+    assert r["iters"] == 4 and r["changed"] == 0
+    # both loops stop with dV < tol under a gamma-contraction: |V_PI - V*| <= 2*tol*gamma/(1-gamma)
+    o = oracle.value_iteration(0, cells, dtype="f64", slip_p=0.9)
+    assert np.abs(r["V"] - o["V"]).max() <= 2 * 1e-6 * 0.99 / (1 - 0.99)
+    # max_iters = 1: one evaluation, one improvement
+    r1 = ref.policy_iteration(np.full((4, ref.S), 6, np.int8), max_iters=1)
+    assert r1["iters"] == 1 and r1["changed"] > 0 and r1["changes"] == [r["changes"][0]]
+
+
+def test_front_end_refuses_bad_shapes_and_dtypes_before_device_work():
+    """_check_policy needs no handle state beyond B and S: shape and dtype errors are ValueError."""
+    vi = mg.ValueIteration.__new__(mg.ValueIteration)
+    vi.B, vi.S = 2, 100
+    with pytest.raises(ValueError, match="shape"):
+        vi._check_policy(np.zeros((2, 99), np.int8))
+    with pytest.raises(ValueError, match="integer"):
+        vi._check_policy(np.zeros((2, 100), np.float32))
+    with pytest.raises(ValueError, match="int8"):
+        vi._check_policy(np.full((2, 100), 300, np.int32))
+    assert vi._check_policy(np.full((2, 100), 3, np.int64)).dtype == np.int8
+    vi.h = None  # nothing to destroy
