@@ -295,7 +295,6 @@ using N1to8 = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;  // wave2, ban
 using NWave = std::integer_sequence<int, 1, 2, 4, 8>;              // lone wave: cells per lane
 using NMix = std::integer_sequence<int, 2, 3, 4, 5, 6>;            // mix (fp32)
 using NWave2n = std::integer_sequence<int, 2, 3, 4>;               // wave2n: blocks per wave
-using NPairPlane = std::integer_sequence<int, 3, 4, 5>;            // serve_pair: plane stride / 64 (65..256 cells, W 9..16)
 
 template <typename T, int MODEL, bool SLIP, int MAP>
 struct Kernels {
@@ -338,10 +337,7 @@ int resolve_kernels(const ViPlan &p, ViKernels *out) {
             if constexpr (std::is_same<T, float>::value)
                 if (p.kern == Loop::mix) fused(pick<KS::template Fused, Loop::mix>(p.n, f, NMix{}));
             if (p.serve_kern == Loop::serve_ew) serve(KS::template Serve<Loop::serve_ew, 0>::fn);
-            // serve_pair: the plane stride at compile time where the plan names one of these; else at run time
-            if (p.serve_kern == Loop::serve_pair)
-                serve(pick<KS::template Serve, Loop::serve_pair>(p.serve_n, KS::template Serve<Loop::serve_pair, 0>::fn,
-                                                                 NPairPlane{}));
+            if (p.serve_kern == Loop::serve_pair) serve(KS::template Serve<Loop::serve_pair, 0>::fn);
             if (p.serve_kern == Loop::band) serve(pick<KS::template Serve, Loop::band>(p.serve_n, s, N1to8{}));
             if (p.wants_bserve) {  // the wave2 loop of the same P (the capacity of both is the same by bserve_min_waves)
                 b = pick<KS::template BServe, Loop::wave2>(p.wave2, b, N1to8{});
@@ -587,7 +583,28 @@ int reduce_env(mgdp_vi *vi, int32_t *kmax, double *dvmax) {
         n += 1;
         solve += (double)(h[9] - h[8]) * 0.01;
         cyc += (double)(h[15] - h[14]);
+        // the pair loop's shader-clock stamps (fused_serve_pair, words 18..23; all 0 on other loops):
+        // seen -> first pair, one steady pair split at reads landed / last VALU / barrier passed, the
+        // whole loop, loop left -> publish
+        static double seg[7] = {0, 0, 0, 0, 0, 0, 0};
+        const volatile unsigned long long *s = h + 18;
+        if (s[0] && s[5]) {
+            seg[0] += (double)(s[0] - h[14]);
+            if (s[1] && s[4]) {
+                seg[1] += (double)(s[2] - s[1]);
+                seg[2] += (double)(s[3] - s[2]);
+                seg[3] += (double)(s[4] - s[3]);
+                seg[4] += (double)(s[4] - s[1]);
+            }
+            seg[5] += (double)(s[5] - s[0]);
+            seg[6] += (double)(h[15] - s[5]);
+        }
         if ((long long)n % 1000 == 0) {
+            std::fprintf(stderr, "serve trace pair: cycles per solve: seen->first pair %.1f, steady pair %.1f = reads %.1f + valu %.1f + "
+                                 "flags/barrier %.1f, loop %.1f, left->publish %.1f, seen->publish %.1f\n",
+                         seg[0] / 1000.0, seg[4] / 1000.0, seg[1] / 1000.0, seg[2] / 1000.0, seg[3] / 1000.0, seg[5] / 1000.0,
+                         seg[6] / 1000.0, cyc / 1000.0);
+            for (double &x : seg) x = 0;
             const double t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_first).count();
             std::fprintf(stderr, "serve trace: solves %.0f-%.0f, t %.1f ms, request seen -> publish %.3f us, sclk %.0f MHz (sweeps %llu)\n",
                          n - 999, n, t_ms, solve / 1000.0, cyc / solve, (unsigned long long)(h[5] & 0xffffffffull));

@@ -296,6 +296,9 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         if (SERVED) {
             if (threadIdx.x == 0) {
 #ifdef MGDP_SERVE_TRACE
+                // the pair loop's stamps of this solve (fused_serve_pair stored them just now), words 18..23
+                for (int i = 0; i < 6; ++i)
+                    __hip_atomic_store(host_out + 18 + i, g_pair_trace[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(host_out + 15, __builtin_amdgcn_s_memtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(host_out + 9, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #endif
@@ -340,10 +343,9 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
             bool ran = false;
             if constexpr (L == Loop::serve_pair) {
                 if (ew) {
-                    // N > 0: the plane stride 64 * N at compile time (the plan's serve_n), a tile = 4 planes
-                    const int te = N > 0 ? 4 * 64 * N : serve_pair_tile_elems(geo.HWs, geo.W);
-                    fused_serve_pair<T, N>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done,
-                                           *pre, *sp, ew == 2);
+                    const int te = serve_pair_tile_elems(geo.HWs, geo.W);  // a tile: [pad][HWs][pad] cells of 4 planes
+                    fused_serve_pair<T>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done,
+                                        *pre, *sp, ew == 2);
                     ran = true;
                 }
             } else if (ew) {

@@ -41,7 +41,8 @@ MGDP_HD inline Smem smem_layout(int S, int HWp, int tsize, int nbuf = 2) {
 // fused_serve_xyd: each tile = [pad][plane 1][pad][plane 3][pad], carved from the two V buffers
 MGDP_HD inline int serve_ew_padw(int W) { return (W + 15) / 16 * 16; }
 MGDP_HD inline int serve_ew_tile_elems(int HWs, int W) { return 2 * HWs + 3 * serve_ew_padw(W); }
-// fused_serve_pair: two tiles of four planes, each [pad][HWs cells][pad], pad = round_up(2W, 16)
+// fused_serve_pair: two cell-major tiles, each [pad][HWs][pad] cells of four planes side by side (16 B for
+// fp32), pad = round_up(2W, 16) cells; serve_pair_plane is a tile's cells, with the pads
 MGDP_HD inline int serve_pair_pad(int W) { return (2 * W + 15) / 16 * 16; }
 MGDP_HD inline int serve_pair_plane(int HWs, int W) { return HWs + 2 * serve_pair_pad(W); }
 MGDP_HD inline int serve_pair_tile_elems(int HWs, int W) { return 4 * serve_pair_plane(HWs, W); }

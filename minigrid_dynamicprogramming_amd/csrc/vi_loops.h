@@ -593,8 +593,10 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
 //    first-sweep arithmetic only, a stop on its first sweep that and the pair's second sweep
 //    (Empty-16's 29 sweeps from 0 end on a second sweep).
 //  * Three register sets rotate (in, middle, out) with the two tiles: the loop is unrolled by six
-//    pairs.  LDS: two tiles of four planes, each [pad][HWs cells][pad], pad = round_up(2W, 16), the
-//    host sizes the V buffers for them (serve_pair_tile_elems).
+//    pairs.  LDS: two cell-major tiles, each [pad][HWs cells][pad] with a cell's four planes side by
+//    side, pad = round_up(2W, 16) cells of +0; the host sizes the V buffers for them (serve_pair_tile_elems).
+//    A pair is one 16-byte store and four data reads (cells c + W and c - W whole, one plane of c + 2W
+//    and of c - 2W) for fp32.
 // Requires k < max_sweeps on entry (fused_grid only calls with work to do).
 
 // The pair loop's neighbour topology of thread t (resolved once per grid by the server): bit 0 the
@@ -630,9 +632,18 @@ __device__ __forceinline__ ServePairTopo<T> serve_pair_topo(const uint8_t *cl, c
     return s;
 }
 
-// NPL > 0: the plane stride is 64 * NPL elements, known at compile time (the plan's serve_n), so every
-// plane of a cell is an immediate offset from one address register; 0: serve_pair_plane at run time.
-template <typename T, int NPL, typename Done>
+#ifdef MGDP_SERVE_TRACE
+// Trace build only: shader-clock stamps (s_memtime) of one solve's pair loop, taken by
+// every wave in SGPRs and stored by thread 0 when the loop is left: [0] first pair entered, [1] the
+// pair that starts at sweep count kPairTraceK entered, [2] its reads landed, [3] its last VALU result
+// made, [4] its barrier passed, [5] loop left.  The server copies them into spare host words.
+static __shared__ unsigned long long g_pair_trace[6];
+constexpr int kPairTraceK = 5;  // the third pair of a fresh solve: steady state
+#define MGDP_PAIR_STAMP(i) do { if (k == kPairTraceK) tr[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define MGDP_PAIR_STAMP(i) do { } while (0)
+#endif
+template <typename T, typename Done>
 __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &cf, T *T0, T *T1, T *slots,
                                                  uint8_t *flags, const T *Vg, T *Vg_out, int8_t *pig, int &k,
                                                  double &dvl, const Done &done, const XydTopo<T> &tp,
@@ -640,9 +651,15 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     const int c = threadIdx.x, lane = c & 63;
     const int cc = c < geo.HW ? c : 0;
     const bool own_cell = c < geo.HW;
-    const int W = geo.W, PL = NPL > 0 ? 64 * NPL : serve_pair_plane(geo.HWs, W);
+    const int W = geo.W;
     k = __builtin_amdgcn_readfirstlane(k);  // uniform: the sweep count in an SGPR
-    const int o0 = serve_pair_pad(W) + c;  // plane d of this cell at d * PL + o0
+    // The tiles are cell-major: plane d of this cell at element 4 * o0 + d, so a cell's four planes are one
+    // 16-byte access for fp32 (ds_read_b128 / ds_write_b128; two for fp64) and consecutive lanes touch
+    // consecutive 16-byte slots (no bank conflict in any of ds_read_b128's 16-lane groups, at any +-W offset).
+    const int o0 = serve_pair_pad(W) + c;
+    struct alignas(16) C4 { T v[4]; };
+    auto cell = [&](const T *t, int off) -> C4 { return *reinterpret_cast<const C4 *>(t + 4 * (o0 + off)); };
+    auto put = [&](T *t, const T (&v)[4]) { *reinterpret_cast<C4 *>(t + 4 * o0) = C4{{v[0], v[1], v[2], v[3]}}; };
     const T ge = sp.ge;
     T tq[4];  // the goal rewards in registers for the loop (the server's topology may live in memory)
 #pragma unroll
@@ -662,8 +679,8 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
         for (int d = 0; d < 4; ++d) A[d] = own_cell ? x.v[d] : (T)0;
     }
     if (zero_tiles) {
-        const int te = 4 * PL;
-        for (int i = c; i < te; i += sp.block) {  // pads (and planes) of both tiles start at +0
+        const int te = serve_pair_tile_elems(geo.HWs, W);
+        for (int i = c; i < te; i += sp.block) {  // pads (and cells) of both tiles start at +0
             T0[i] = (T)0;
             T1[i] = (T)0;
         }
@@ -687,8 +704,8 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
             B[d] = (T)0;
             C[d] = vmax((T)0, tq[d]);
             dm = vmax(dm, C[d]);
-            T1[d * PL + o0] = C[d];
         }
+        put(T1, C);
         const uint32_t bits = 1u | (__ballot(dm >= cf.tol) != 0ull && 1 < geo.max_sweeps ? 2u : 0u);
         if (lane0) {
             fwave[0] = (uint8_t)bits;
@@ -702,11 +719,14 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
         for (int d = 0; d < 4; ++d) {
             B[d] = (T)0;
             C[d] = (T)0;
-            T0[d * PL + o0] = A[d];
         }
+        put(T0, A);
         __syncthreads();
     }
     int stop = 0;  // 1: K = k - 1, 2: K = k
+#ifdef MGDP_SERVE_TRACE
+    unsigned long long tr[6] = {0, 0, 0, 0, 0, 0};
+#endif
     // one sweep of this lane's cell from its own values and its four geometric fronts (fused_serve_xyd's)
     auto step = [&](const T (&in)[4], const T fE, const T fS, const T fW, const T fN, T (&out)[4]) -> T {
         const T m02 = vmax(in[0], in[2]), m13 = vmax(in[1], in[3]);
@@ -727,8 +747,12 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     auto pair = [&](const T *Tin, T *Tout, const T (&in)[4], T (&mid)[4], T (&out)[4], const int par,
                     auto test, auto half) -> bool {
         constexpr bool HALF = decltype(half)::value;
+        MGDP_PAIR_STAMP(1);
         const uint32_t fl = *reinterpret_cast<const uint32_t *>(flags + (par ^ 1) * 16);
-        const T fS = Tin[PL + o0 + W], fN = Tin[3 * PL + o0 - W];
+        // the whole cells c + W and c - W (16 bytes each for fp32): the own fronts and three of the four
+        // values each neighbour's sweep k+1 needs
+        const C4 cS = cell(Tin, W), cN = cell(Tin, -W);
+        const T fS = cS.v[1], fN = cN.v[3];
         T dm1 = (T)0, vS, vN;
         if (HALF) {
 #pragma unroll
@@ -736,13 +760,22 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
             vS = fS;
             vN = fN;
         } else {
-            const T s0 = Tin[o0 + W], s2 = Tin[2 * PL + o0 + W], sf = Tin[PL + o0 + 2 * W];
-            const T n0 = Tin[o0 - W], n2 = Tin[2 * PL + o0 - W], nf = Tin[3 * PL + o0 - 2 * W];
+            const T s0 = cS.v[0], s2 = cS.v[2], sf = Tin[4 * (o0 + 2 * W) + 1];
+            const T n0 = cN.v[0], n2 = cN.v[2], nf = Tin[4 * (o0 - 2 * W) + 3];
+#ifdef MGDP_SERVE_TRACE
+            if (k == kPairTraceK) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                tr[2] = __builtin_amdgcn_s_memtime();
+            }
+#endif
             dm1 = step(in, dpp_shl1_zero(in[0]), fS, dpp_shr1_zero(in[2]), fN, mid);
             // sweep k+1 of plane 1 of c + W and plane 3 of c - W (their owners' arithmetic)
             vS = vmax(geS * vmax(vmax(s0, s2), vmax(fS, sf)), tqS);
             vN = vmax(geN * vmax(vmax(n0, n2), vmax(fN, nf)), tqN);
             asm volatile("" ::"v"(vS), "v"(vN));  // reads and arithmetic ahead of the test (not sunk past it)
+            // the two planes not used count as used, here and not at the reads (that would wait for them):
+            // whole cells, one 16-byte read each (else the compiler reads 12 bytes, or 4 + 8)
+            asm volatile("" ::"v"(cS.v[3]), "v"(cN.v[1]));
         }
         // the last pair's sweeps k - 1 and k (a bit is 0 when that sweep's |dV| < tol everywhere in the
         // wave or it reached max_sweeps)
@@ -751,8 +784,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
             if ((fl & 0x02020202u) == 0u) { stop = 2; return false; }
         }
         const T dm2 = step(mid, dpp_shl1_zero(mid[0]), vS, dpp_shr1_zero(mid[2]), vN, out);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) Tout[d * PL + o0] = out[d];
+        put(Tout, out);
         constexpr int n = HALF ? 1 : 2;  // sweeps this call computes
         // The sweep counts are made ahead of the tests, not inside their short-circuit arms: there the
         // compiler re-used k + n for the count on one side of lane 0's branch only, and each pair carried a
@@ -761,11 +793,16 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
         const uint32_t bits = (HALF || (__ballot(dm1 >= cf.tol) != 0ull && k1 < geo.max_sweeps) ? 1u : 0u) |
                               (__ballot(dm2 >= cf.tol) != 0ull && kn < geo.max_sweeps ? 2u : 0u);
         if (lane0) fwave[par * 16] = (uint8_t)bits;
+#ifdef MGDP_SERVE_TRACE
+        asm volatile("" ::"v"(dm2));
+        MGDP_PAIR_STAMP(3);
+#endif
         dm1p = dm1;
         dm2p = dm2;
         vSp = vS;
         vNp = vN;
         __syncthreads();
+        MGDP_PAIR_STAMP(4);
         k = kn;
         return true;
     };
@@ -776,6 +813,9 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     // output tile (T0 for even p) still holds V_{k-2}, the last pair's input.
     int p;
     if (!fresh) pair(T0, T1, A, B, C, 0, No{}, Yes{});
+#ifdef MGDP_SERVE_TRACE
+    tr[0] = __builtin_amdgcn_s_memtime();
+#endif
     while (true) {
         if (!pair(T1, T0, C, A, B, 1, Yes{}, No{})) { p = 0; break; }
         if (!pair(T0, T1, B, C, A, 0, Yes{}, No{})) { p = 1; break; }
@@ -784,6 +824,11 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
         if (!pair(T1, T0, B, C, A, 1, Yes{}, No{})) { p = 4; break; }
         if (!pair(T0, T1, A, B, C, 0, Yes{}, No{})) { p = 5; break; }
     }
+#ifdef MGDP_SERVE_TRACE
+    tr[5] = __builtin_amdgcn_s_memtime();
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 6; ++i) g_pair_trace[i] = tr[i];
+#endif
     const T diff = stop == 1 ? dm1p : dm2p;
     if (stop == 1) k -= 1;
     dvl = (double)block_max_nw(diff, slots, 0, (int)threadIdx.x, sp.block >> 6);
@@ -799,13 +844,18 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     const T *Tp = (p & 1) ? T1 : T0;  // V_{k-2}, all four planes
     // V_K and V_{K-1}, and V_{K-1}'s fronts
     T vk[4], vp[4];
+    C4 prev = {{vk1[0], vk1[1], vk1[2], vk1[3]}};
+    T pS = vSp, pN = vNp;
+    if (stop == 1) {  // uniform: V_{k-2} and its fronts from the tile
+        prev = cell(Tp, 0);
+        pS = Tp[4 * (o0 + W) + 1];
+        pN = Tp[4 * (o0 - W) + 3];
+    }
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         vk[d] = stop == 1 ? vk1[d] : vk_[d];
-        vp[d] = stop == 1 ? Tp[d * PL + o0] : vk1[d];
+        vp[d] = prev.v[d];
     }
-    const T pS = stop == 1 ? Tp[PL + o0 + W] : vSp;
-    const T pN = stop == 1 ? Tp[3 * PL + o0 - W] : vNp;
     const T pE = dpp_shl1_zero(vp[0]), pW = dpp_shr1_zero(vp[2]);
     if (own_cell) {
         // forward reads the front state when the agent can enter it, else its own (xyd_step's nbv)

@@ -350,10 +350,6 @@ inline ViPlan plan_vi(const mgdp_vi_desc &d, const ViKnobs &kn) {
     if (xyd && cell) {
         if (p.cpt == 2) p.serve_kern = p.serve_loop = Loop::xyd_x2, p.serve_n = 0;
         if (det && serve_ew) p.serve_kern = p.serve_loop = serve_pair ? Loop::serve_pair : Loop::serve_ew, p.serve_n = 0;
-        // the pair loop's plane stride in blocks of 64 elements when it is a whole number of them (every
-        // grid of width 9..16: HWs + 64), for the kernels that hold it at compile time; else 0
-        if (det && serve_ew && serve_pair && serve_pair_plane(p.HWs, d.W) % 64 == 0)
-            p.serve_n = serve_pair_plane(p.HWs, d.W) / 64;
         if (det && band) p.serve_kern = p.serve_loop = Loop::band, p.serve_n = band;
     }
     if (dk && cell && det && dkhalf) p.serve_kern = p.serve_loop = Loop::dk_half, p.serve_n = p.HWs / 64;
