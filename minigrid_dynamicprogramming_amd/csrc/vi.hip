@@ -577,6 +577,14 @@ int reduce_env(mgdp_vi *vi, int32_t *kmax, double *dvmax) {
 #ifdef MGDP_SERVE_TRACE
     // trace build (tools/probe_serve_trace.sh): server-side s_memrealtime stamps, 10 ns ticks --
     // [8] request seen by the workgroup, [9] result about to be published
+    // The server stores its stamps behind the result (so the publish is the plain build's), word 9 last:
+    // wait for it to change (bounded: a relaunched server's first solve may repeat nothing).
+    if (tagged) {
+        static unsigned long long last9 = 0;
+        for (int spin = 0; spin < 100000 && h[9] == last9; ++spin) __builtin_ia32_pause();
+        last9 = h[9];
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
     if (tagged) {  // each block of 1000 solves: mean GPU-side time, the shader clock over it, and when
         static double n = 0, solve = 0, cyc = 0;
         static const auto t_first = std::chrono::steady_clock::now();

@@ -296,13 +296,18 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         if (SERVED) {
             if (threadIdx.x == 0) {
 #ifdef MGDP_SERVE_TRACE
+                // the stamps are taken in front of the publish and stored behind it, so that "loop left ->
+                // publish" is the plain build's path; the host waits for word 9, stored last
+                const unsigned long long c_pub = __builtin_amdgcn_s_memtime(), t_pub = __builtin_amdgcn_s_memrealtime();
+#endif
+                publish_tagged(host_out, kk, dv, epoch);
+#ifdef MGDP_SERVE_TRACE
                 // the pair loop's stamps of this solve (fused_serve_pair stored them just now), words 18..23
                 for (int i = 0; i < 6; ++i)
                     __hip_atomic_store(host_out + 18 + i, g_pair_trace[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_out + 15, __builtin_amdgcn_s_memtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_out + 9, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(host_out + 15, c_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(host_out + 9, t_pub, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 #endif
-                publish_tagged(host_out, kk, dv, epoch);
             }
         } else if (lone && threadIdx.x == 0) {
             publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),

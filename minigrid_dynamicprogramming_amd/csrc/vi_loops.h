@@ -632,6 +632,28 @@ __device__ __forceinline__ ServePairTopo<T> serve_pair_topo(const uint8_t *cl, c
     return s;
 }
 
+// The pair loop's exit reduction: the workgroup's max |dV| of the stopping sweep on at most
+// four waves, one barrier and one LDS read.  Lane 0 of each wave stores the wave's max into its own slot
+// of slots[kServePairSlot .. + 3]; after the barrier every lane reads the four slots at once (16 bytes for
+// fp32).  The slots of waves the workgroup does not have hold +0 from the grid's first solve
+// (fused_serve_pair, zero_tiles), neutral as every |dV| is >= +0.  No other loop of the served kernels
+// touches these four: block_max_nw writes slots[parity * 16 + wave], wave < 4 (256 threads at most).
+// A wave whose lanes all hold +0 -- every wave of a stop at an exact fixed point, a wave of walls at any
+// stop -- stores +0 without the DPP chain: the same bits as the max of its zeros.
+// Max over values that are +0 or positive is exact, associative and commutative, so the result is
+// block_max_nw's bit for bit, whatever the order.
+constexpr int kServePairSlot = 4;
+template <typename T>
+__device__ __forceinline__ T serve_pair_max(T v, T *slots, int wave, bool lane0) {
+    T m = (T)0;
+    if (__ballot(v != (T)0) != 0ull) m = wave_max(v);  // uniform branch
+    struct alignas(16) S4 { T v[4]; };  // the slots start on a 16-byte boundary (smem_layout)
+    if (lane0) slots[kServePairSlot + wave] = m;
+    __syncthreads();
+    const S4 s = *reinterpret_cast<const S4 *>(slots + kServePairSlot);
+    return vmax(vmax(vmax(s.v[0], s.v[1]), s.v[2]), s.v[3]);
+}
+
 #ifdef MGDP_SERVE_TRACE
 // Trace build only: shader-clock stamps (s_memtime) of one solve's pair loop, taken by
 // every wave in SGPRs and stored by thread 0 when the loop is left: [0] first pair entered, [1] the
@@ -686,6 +708,9 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
         }
         // the fresh start leaves the flag bytes of waves the workgroup does not have alone: +0 once per grid
         if (c < 64) flags[c] = 0;
+        // likewise the exit reduction's slots (serve_pair_max): a wave the workgroup has rewrites its own
+        // at every stop, the others stay +0
+        if (c < 4) slots[kServePairSlot + c] = (T)0;
         __syncthreads();
     }
     if (fresh) {
@@ -831,7 +856,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
 #endif
     const T diff = stop == 1 ? dm1p : dm2p;
     if (stop == 1) k -= 1;
-    dvl = (double)block_max_nw(diff, slots, 0, (int)threadIdx.x, sp.block >> 6);
+    dvl = (double)serve_pair_max(diff, slots, (int)(threadIdx.x >> 6), lane0);
     done(k, dvl);
     // element selects (a pointer to one of the sets would put them in scratch)
     const int r = p % 3;
