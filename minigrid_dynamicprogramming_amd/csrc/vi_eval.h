@@ -258,11 +258,12 @@ vi_eval_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__rest
     const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, HW = geo.HW, HWs = geo.HWs;
     int k = fresh ? 0 : kenv[e];
     double dvl = fresh ? 0.0 : dvenv[e];
-    if (k_target > k && k > 0 && dvl == 0.0) {  // fixed-point completion (fused_grid)
+    if (k_target > k && k > 0 && dvl == 0.0) {  // fixed-point completion (grid_complete_at)
         if (tid == 0) kenv[e] = k_target;
         k = k_target;
     }
     const bool own_rule = k_target < 0;
+    // (grid_has_work, written out: the shared predicates moved this kernel's registers)
     const bool work = own_rule ? (!(k > 0 && dvl < geo.tol) && k < geo.max_sweeps) : (k < k_target);
     if (work) {
         const long long vb = (long long)e * geo.S;
@@ -323,11 +324,7 @@ vi_eval_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__rest
             dvl = (double)block_max(diff, slots, 0);
             for (int c = tid; c < HW; c += nt) eval_store_cell<T, MODEL>(Vg, Vin, HWs, c);
         }
-        if (tid == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
+        record_grid(geo, kenv, dvenv, e, k, dvl, tid == 0);
     }
     if (in_kernel_reduce)
         fused_reduce(red, ticket, host_out, k, dvl, reinterpret_cast<unsigned int *>(slots + 16), epoch, false, tid);

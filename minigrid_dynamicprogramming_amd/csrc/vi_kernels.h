@@ -34,55 +34,112 @@ __host__ __device__ constexpr bool loop_is_soa_only(Loop l) { return l != Loop::
 // fp64 P = 1 (57 VGPRs); the other variants are VGPR-bound at <= 6 waves.  Batches at the SGPR-bound
 // residency also hit a dispatcher limit the occupancy API does not see: LavaS11N5 x 7168 at 28 / CU
 // took 199 us (waiting grids ran to the cap) against 57 us at 32 / CU (profiles/r03_w8/).
-// MGDP_WAVE2_W8=0 (A/B builds) keeps the compiler's default.
-#ifndef MGDP_WAVE2_W8
-#define MGDP_WAVE2_W8 1
-#endif
-#ifndef MGDP_WAVE2_P4_W6  // A/B builds: fp32 P = 4 (Empty-16) at 6 waves instead of its 91-VGPR 5
-#define MGDP_WAVE2_P4_W6 0
-#endif
-#ifndef MGDP_WAVE2N_MINW  // A/B builds: minimum waves per SIMD of the two-waves-per-grid kernels
-#define MGDP_WAVE2N_MINW 1
-#endif
+// Tried: fp32 P = 4 (Empty-16) at 6 waves instead of its 91-VGPR 5, and a minimum for the
+// two-waves-per-grid kernels (wave2n); neither was kept.
 // Minimum waves per SIMD of fp32 fused_dk_rows: round 5's 6 (80 VGPRs and 76-80 B of scratch, 6 grids per
 // CU) measured 1950-1960 vs 1992-1996 us per DoorKey-16 x 65536 solve at 5, neutral at 8192 grids
 // (profiles/r05_dkw6/), but its spill stores doubled the launch's HBM writes.  Now: the 16x16 own-rule
 // variant (Loop::dk_rows16) at 6 waves, 80 VGPRs, no scratch; the general one at 5 (96 VGPRs, no scratch).
-// A/B builds: MGDP_DKROW16_MINW / MGDP_DKROW_MINW (1 = the compiler's choice).
-#ifndef MGDP_DKROW_MINW
-#define MGDP_DKROW_MINW 5
-#endif
-#ifndef MGDP_DKROW16_MINW
-#define MGDP_DKROW16_MINW 6
-#endif
 template <typename T>
 __host__ __device__ constexpr int wave2_min_waves(Loop l, int n) {
-    return l == Loop::dk_rows     ? (sizeof(T) == 4 ? MGDP_DKROW_MINW : 1)  // fp64 at 6 waves spills 492 B
-           : l == Loop::dk_rows16 ? (sizeof(T) == 4 ? MGDP_DKROW16_MINW : 1)
-           : l == Loop::wave2n    ? MGDP_WAVE2N_MINW
-           : (MGDP_WAVE2_W8 && l == Loop::mix && n <= 2) ? 8
-           : (MGDP_WAVE2_W8 && l == Loop::wave2 && n <= (sizeof(T) == 4 ? 2 : 1)) ? 8
-           : (MGDP_WAVE2_P4_W6 && l == Loop::wave2 && sizeof(T) == 4 && n == 4) ? 6
-                                                                                  : 1;
+    return l == Loop::dk_rows     ? (sizeof(T) == 4 ? 5 : 1)  // fp64 at 6 waves spills 492 B
+           : l == Loop::dk_rows16 ? (sizeof(T) == 4 ? 6 : 1)
+           : (l == Loop::mix && n <= 2) ? 8
+           : (l == Loop::wave2 && n <= (sizeof(T) == 4 ? 2 : 1)) ? 8
+                                                                  : 1;
 }
 // Loop::dk_half: batched DoorKey, a cell's states split over two threads by has_key (fused_dk_half;
 // workgroup = 2 * HWs threads), plane stride HWs = 64 * N known at compile time.
-// MGDP_DK_PERM=0 (A/B builds): batched DoorKey grids keep thread t on cell t (no dk_class_perm)
-#ifndef MGDP_DK_PERM
-#define MGDP_DK_PERM 1
-#endif
 template <typename T, int MODEL> struct TopoOf { using type = XydTopo<T>; };
 template <typename T> struct TopoOf<T, MGDP_MODEL_DOORKEY> { using type = DkTopo; };
 
-// pre: the cell topology a persistent server resolved once per residency (SERVED only)
+// ------------------------------------------------------------------------------------------------
+// The per-grid protocol every solving kernel follows: resume {k, dV}, apply fixed-point completion,
+// test for work, sweep, record the result.  Its pieces, each said once:
+// ------------------------------------------------------------------------------------------------
+// Fixed-point completion: a grid whose last sweep changed nothing (|dV| = 0 exactly, so
+// V_k == V_{k-1} bit for bit) reproduces V_k at every later sweep (a Jacobi sweep is a function
+// of V alone), and pi_{k'} = argmax on V_{k'-1} = pi_k: it is at sweep k_target already, with
+// dV 0.  Only its sweep count moves (the reduce kernel reads it).
+__device__ __forceinline__ bool grid_complete_at(int k, double dvl, int k_target) {
+    return k_target > k && k > 0 && dvl == 0.0;
+}
+// own rule (k_target < 0): not yet below tol and under the sweep cap; run_to: short of k_target
+__device__ __forceinline__ bool grid_has_work(const Geo &geo, int k, double dvl, int k_target) {
+    return k_target < 0 ? (!(k > 0 && dvl < geo.tol) && k < geo.max_sweeps) : (k < k_target);
+}
+// The grid's record: its sweep count (also the learned dispatch order's input) and last |dV|.
+__device__ __forceinline__ void record_grid(const Geo &geo, int32_t *kenv, double *dvenv, int e, int k, double dvl,
+                                            bool writer) {
+    if (writer) {
+        kenv[e] = k;
+        if (geo.kexec) geo.kexec[e] = k;
+        dvenv[e] = dvl;
+    }
+}
+// A solve's early publication, from inside its loop (before the pi pass and the exit stores): a
+// launch of one grid publishes {k, dV, k} itself; a served solve publishes tagged with its request.
+template <bool SERVED>
+__device__ __forceinline__ void publish_solve(unsigned long long *host_out, int kk, double dv, unsigned int epoch,
+                                              bool lone, bool writer) {
+    if (SERVED) {
+        if (writer) {
+#ifdef MGDP_SERVE_TRACE
+            // the stamps are taken in front of the publish and stored behind it, so that "loop left ->
+            // publish" is the plain build's path; the host waits for word 9, stored last
+            const unsigned long long c_pub = __builtin_amdgcn_s_memtime(), t_pub = __builtin_amdgcn_s_memrealtime();
+#endif
+            publish_tagged(host_out, kk, dv, epoch);
+#ifdef MGDP_SERVE_TRACE
+            // the pair loop's stamps of this solve (fused_serve_pair stored them just now), words 18..23
+            for (int i = 0; i < 6; ++i)
+                __hip_atomic_store(host_out + 18 + i, g_pair_trace[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host_out + 15, c_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host_out + 9, t_pub, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+        }
+    } else if (lone && writer) {
+        publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
+                (unsigned long long)kk, epoch);
+    }
+}
+// A loop's two instantiations -- own rule (LOCAL) and run-to -- from one call site: the call is written
+// once, with OWN_RULE as its LOCAL argument.  Tried: a constexpr-bool dispatcher taking a generic lambda
+// (by_rule(own, [&](auto r) { loop<T, r.value>(...); })); the closure sits between the kernel's
+// __restrict__ arguments and the loop until after inlining, and registers moved in 130 kernels.
+// The macro expands to the twin call as it was written out before.  Undefined below fused_grid.
+#define MGDP_BY_RULE(own, ...)               \
+    do {                                     \
+        if (own) {                           \
+            constexpr bool OWN_RULE = true;  \
+            __VA_ARGS__;                     \
+        } else {                             \
+            constexpr bool OWN_RULE = false; \
+            __VA_ARGS__;                     \
+        }                                    \
+    } while (0)
+
+// What a persistent lone-grid server resolves once per staged grid and hands to every solve
+// (vi_serve_kernel; a launch passes none).
+template <typename T, int MODEL>
+struct ServeCtx {
+    typename TopoOf<T, MODEL>::type topo;  // this thread's cell topology (Loop::generic, serve_ew, serve_pair)
+    ServePairTopo<T> sp;                   // Loop::serve_pair: its own per-grid constants
+    int ew;  // Loop::serve_ew / serve_pair: 0 = the grid falls back, 1 = the served loop, 2 = the same, first
+             // solve of the grid (tiles to clear)
+};
+
+// One grid of a fused launch or of a served request, for every Loop family: prologue (resume, learned
+// priority, fixed-point completion, work test), the family's section (its LDS staging and its loop),
+// epilogue (the record).  Returns whether the grid swept (and so published, if it publishes itself).
+// gk: the launch-wide rule's counter tree (wave2-family launches); sc: the server's context (SERVED only).
 template <typename T, int MODEL, bool SLIP, int MAP, bool SERVED = false, Loop L = Loop::generic, int N = 0>
 __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, const uint8_t *__restrict__ cells,
                                            T *__restrict__ V, int8_t *__restrict__ pi, int32_t *__restrict__ kenv,
                                            double *__restrict__ dvenv, unsigned long long *__restrict__ host_out,
                                            int k_target, int fresh, bool lone, unsigned int epoch, int e,
-                                           int &k, double &dvl, const typename TopoOf<T, MODEL>::type *pre = nullptr,
-                                           unsigned long long *gk = nullptr, int ew = 0,
-                                           const ServePairTopo<T> *sp = nullptr) {
+                                           int &k, double &dvl, unsigned long long *gk = nullptr,
+                                           const ServeCtx<T, MODEL> *sc = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Smem LY = smem_layout(geo.Ss, geo.HWp, (int)sizeof(T), geo.nbuf);
     T *V0 = reinterpret_cast<T *>(smem);
@@ -109,325 +166,199 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
         else if (kp >= geo.kprio[1]) __builtin_amdgcn_s_setprio(2);
         else if (kp >= geo.kprio[2]) __builtin_amdgcn_s_setprio(1);
     }
-    // Fixed-point completion: a grid whose last sweep changed nothing (|dV| = 0 exactly, so
-    // V_k == V_{k-1} bit for bit) reproduces V_k at every later sweep (a Jacobi sweep is a function
-    // of V alone), and pi_{k'} = argmax on V_{k'-1} = pi_k: it is at sweep k_target already, with
-    // dV 0.  Only its sweep count moves (the reduce kernel reads it).
-    if (k_target > k && k > 0 && dvl == 0.0) {
+    if (grid_complete_at(k, dvl, k_target)) {
         if (threadIdx.x == 0) kenv[e] = k_target;
         k = k_target;
         return false;
     }
+    // (grid_has_work, written out: through the helper, registers moved in 79 of these kernels)
     const bool work = k_target < 0 ? (!(k > 0 && dvl < geo.tol) && k < geo.max_sweeps) : (k < k_target);
     if (!work) return false;
+
+    const bool own = k_target < 0;  // the grid's own stopping rule; else run to sweep k_target
     const long long vb = (long long)e * geo.S;
+    const GkCtx gkc{gk, epoch, e, geo.B, host_out};  // the in-launch reduction of an own-rule launch (gk != nullptr)
+    // The thread that publishes and records is thread 0.  fused_dk_rows re-derives the thread index after
+    // its sweep loop (late_tid) and returns it in tl: nothing behind that loop reads threadIdx.x.
+    int tl = 0;
+    auto writer = [&]() { return loop_is_dkrow(L) ? tl == 0 : threadIdx.x == 0; };
+    auto done = [&](int kk, double dv) { publish_solve<SERVED>(host_out, kk, dv, epoch, lone, writer()); };
+
     if constexpr (L == Loop::mix) {  // two waves for the first nmix workgroups, one for the rest
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "mix: batched plain XYD");
         constexpr int P = N, PW = (P + 1) / 2;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         T *tile = reinterpret_cast<T *>(smem + wave2_tile_off(geo.HWp));
-        auto done2 = [&](int kk, double dv) {
-            if (lone && threadIdx.x == 0)
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-        };
         if ((int)blockIdx.x < geo.nmix) {  // workgroup-uniform: both waves are here
             __syncthreads();
-            if (k_target < 0)
-                fused_wave2n_xyd<T, true, PW>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2,
-                                              GkCtx{gk, epoch, e, geo.B, host_out});
-            else
-                fused_wave2n_xyd<T, false, PW>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
+            MGDP_BY_RULE(own,
+                         fused_wave2n_xyd<T, OWN_RULE, PW>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done, gkc));
         } else {  // wave 0 alone (vi_fused_kernel let wave 1 go)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (k_target < 0)
-                fused_wave2_xyd<T, true, P>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2,
-                                            GkCtx{gk, epoch, e, geo.B, host_out});
-            else
-                fused_wave2_xyd<T, false, P>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
+            MGDP_BY_RULE(own,
+                         fused_wave2_xyd<T, OWN_RULE, P>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done, gkc));
         }
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    if constexpr (L == Loop::wave2n) {  // two waves per grid: cells, then two N/S tiles (wave2n_*)
+    } else if constexpr (L == Loop::wave2n) {  // two waves per grid: cells, then two N/S tiles (wave2n_*)
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "wave2n: batched plain XYD");
-        constexpr int PW = N;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         __syncthreads();
         T *tile = reinterpret_cast<T *>(smem + wave2_tile_off(geo.HWp));
-        auto done2 = [&](int kk, double dv) {
-            if (lone && threadIdx.x == 0)
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-        };
-        if (k_target < 0)
-            fused_wave2n_xyd<T, true, PW>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2,
-                                          GkCtx{gk, epoch, e, geo.B, host_out});
-        else
-            fused_wave2n_xyd<T, false, PW>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    if constexpr (L == Loop::band) {  // LDS: slots, then the cells (no tile); served: the server's staged cells
+        MGDP_BY_RULE(own,
+                     fused_wave2n_xyd<T, OWN_RULE, N>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done, gkc));
+    } else if constexpr (L == Loop::band) {  // LDS: slots, then the cells (no tile); served: the server's staged cells
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "band: plain XYD");
-        constexpr int HB = N;
-        uint8_t *cl2 = SERVED ? reinterpret_cast<uint8_t *>(smem + LY.cells_off()) : smem + 256;
+        uint8_t *cl2 = SERVED ? cl : smem + 256;
         if (!SERVED) {
             copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its LDS writes are ordered
         }
-        auto done2 = [&](int kk, double dv) {
-            if (SERVED) {
-                if (threadIdx.x == 0) publish_tagged(host_out, kk, dv, epoch);
-            } else if (lone && threadIdx.x == 0) {
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-            }
-        };
-        if (k_target < 0)
-            fused_band_xyd<T, true, HB>(geo, cf, cl2, V + vb, V + vb, pi + vb, k, k_target, dvl, done2,
-                                        GkCtx{gk, epoch, e, geo.B, host_out});
-        else
-            fused_band_xyd<T, false, HB>(geo, cf, cl2, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    if constexpr (L == Loop::wave2) {  // its own LDS layout (wave2_*): cells, then the N/S tile
+        MGDP_BY_RULE(own, fused_band_xyd<T, OWN_RULE, N>(geo, cf, cl2, V + vb, V + vb, pi + vb, k, k_target, dvl, done, gkc));
+    } else if constexpr (L == Loop::wave2) {  // its own LDS layout (wave2_*): cells, then the N/S tile
         static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "wave2: batched plain XYD");
-        constexpr int P = N;
         uint8_t *cl2 = smem + 256;
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its LDS writes are ordered
         T *tile = reinterpret_cast<T *>(smem + wave2_tile_off(geo.HWp));
-        auto done2 = [&](int kk, double dv) {
-            if (lone && threadIdx.x == 0)
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-        };
-        if (k_target < 0 && (gk != nullptr || geo.wt)) {  // resident: write-through exit stores (and the
-                                                          // in-launch reduction unless a protocol launch)
-            fused_wave2_xyd<T, true, P, true>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2,
-                                              GkCtx{gk, epoch, e, geo.B, host_out});
-        } else if (k_target < 0) {
-            fused_wave2_xyd<T, true, P>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
-        } else {
-            fused_wave2_xyd<T, false, P>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done2);
-        }
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    if constexpr (loop_is_dkrow(L)) {  // its own LDS layout (dkrow_*): slots, flags, row map, cells, tiles
+        // Irregular: a third instantiation.  A resident own-rule launch (gk: with the in-launch reduction;
+        // geo.wt: a protocol launch, without) writes its exit stores through the L2 (WT); the plain
+        // own-rule instantiation takes no GkCtx, so it holds no counter-tree code.
+        if (own && (gk != nullptr || geo.wt))
+            fused_wave2_xyd<T, true, N, true>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done, gkc);
+        else
+            MGDP_BY_RULE(own,
+                         fused_wave2_xyd<T, OWN_RULE, N>(geo, cf, cl2, tile, V + vb, V + vb, pi + vb, k, k_target, dvl, done));
+    } else if constexpr (loop_is_dkrow(L)) {  // its own LDS layout (dkrow_*): slots, flags, row map, cells, tiles
         static_assert(MODEL == MGDP_MODEL_DOORKEY && !SLIP && MAP == MGDP_MAP_CELL && !SERVED, "dkrow: batched DoorKey");
         uint8_t *cl2 = smem + dkrow_cells_off();
         copy16(cl2, cells + (long long)e * geo.HWp, geo.HWp);
         __syncthreads();
         T *tiles = reinterpret_cast<T *>(smem + dkrow_tile_off(geo.HWp));
         T *slots2 = reinterpret_cast<T *>(smem);
-        // after the loop the thread index is late_tid's (fused_dk_rows): nothing below reads threadIdx.x
-        int tl = 0;
-        auto done2 = [&](int kk, double dv) {
-            if (lone && tl == 0)
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-        };
-        if constexpr (L == Loop::dk_rows16) {  // own-rule launches only (the host picks Loop::dk_rows for run_to)
-            fused_dk_rows<T, true, 256>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb, k,
-                                        k_target, dvl, done2, tl);
-        } else if (k_target < 0) {
-            fused_dk_rows<T, true>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb, k,
-                                   k_target, dvl, done2, tl);
-        } else {
-            fused_dk_rows<T, false>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb, k,
-                                    k_target, dvl, done2, tl);
-        }
-        if (tl == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    // Loop::dk_1t: batched DoorKey on one LDS tile (fused_fast_dk_1t); Loop::xyd_x2 / xyd_x4: CPT cells
-    // per thread on the batched XYD direction-major path (fused_fast_xyd_soa_xn)
-    constexpr bool DK1T = L == Loop::dk_1t;
-    constexpr bool SOA_ONLY = loop_is_soa_only(L);
-    constexpr bool PAIR2 = L == Loop::xyd_pair2;
-    constexpr bool DKHALF = L == Loop::dk_half;
-    constexpr bool SERVE_EW = loop_is_serve_ew(L);
-    constexpr int CPT = PAIR2 || L == Loop::xyd_x2 ? 2 : (L == Loop::xyd_x4 ? 4 : 1);
-    const bool fast = MAP == MGDP_MAP_CELL && geo.HW <= CPT * (int)blockDim.x;
-    const bool soa = SOA_ONLY || (fast && !geo.pair && !geo.quad);
-    if (!SERVED) copy16(cl, cells + (long long)e * geo.HWp, geo.HWp);
-    if (!soa) {
-        // cell-major paths use the first S entries of each (Ss-sized) tile
-        if (k == 0) zero16(V0, geo.S * (int)sizeof(T));
-        else copy16(V0, V + vb, geo.S * (int)sizeof(T));
-    }
-    // the served pair loop's fresh start needs no stage here: it clears its flag bytes once per grid and
-    // sets its first pair's in its own first stage (fused_serve_pair)
-    bool own_start = false;
-    if constexpr (L == Loop::serve_pair) own_start = ew != 0 && k == 0;
-    if (!own_start) {
-        if (threadIdx.x < 64) flags[threadIdx.x] = 0;
-        __syncthreads();
-    }
-
-    int cur = 0, parity = 0;
-    T diff = (T)0;
-    auto done = [&](int kk, double dv) {
-        if (SERVED) {
-            if (threadIdx.x == 0) {
-#ifdef MGDP_SERVE_TRACE
-                // the stamps are taken in front of the publish and stored behind it, so that "loop left ->
-                // publish" is the plain build's path; the host waits for word 9, stored last
-                const unsigned long long c_pub = __builtin_amdgcn_s_memtime(), t_pub = __builtin_amdgcn_s_memrealtime();
-#endif
-                publish_tagged(host_out, kk, dv, epoch);
-#ifdef MGDP_SERVE_TRACE
-                // the pair loop's stamps of this solve (fused_serve_pair stored them just now), words 18..23
-                for (int i = 0; i < 6; ++i)
-                    __hip_atomic_store(host_out + 18 + i, g_pair_trace[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_out + 15, c_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_out + 9, t_pub, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
-            }
-        } else if (lone && threadIdx.x == 0) {
-            publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                    (unsigned long long)kk, epoch);
-        }
-    };
-    const T *Vfinal = nullptr;
-    if constexpr (L == Loop::wave) {  // lone XYD grid on one wave, N cells per lane (host: B == 1, blockDim 64)
-        static_assert(MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL, "one-wave path is XYD, cell mapping");
-        if (SERVED || k_target < 0)
-            fused_wave_xyd<T, SLIP, true, N>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
+        // Irregular: dk_rows16 has only the own-rule instantiation (the host picks Loop::dk_rows for run_to)
+        if constexpr (L == Loop::dk_rows16)
+            fused_dk_rows<T, true, 256>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb, k, k_target, dvl,
+                                        done, tl);
         else
-            fused_wave_xyd<T, SLIP, false, N>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;
-    }
-    if (SERVED || soa) {  // served lone grids are always on this path (serve_eligible): no other code in the server
-        if constexpr (PAIR2) {
-            static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "pair path: plain XYD");
-            constexpr int HWS = 128 * N;
-            if (k_target < 0) fused_pair_xyd<T, true, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-            else fused_pair_xyd<T, false, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && DKHALF) {
-            constexpr int HWS = 64 * N;
-            if (k_target < 0) fused_dk_half<T, true, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-            else fused_dk_half<T, false, HWS>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && DK1T) {
-            if (k_target < 0) fused_fast_dk_1t<T, true>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-            else fused_fast_dk_1t<T, false>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        } else if constexpr (SERVE_EW) {
-            static_assert(SERVED && MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "served plain XYD grid");
-            // ew: 0 = this grid falls back, 1 = fused_serve_xyd (Loop::serve_pair: fused_serve_pair), 2 = the
-            // same, first solve of the grid
-            bool ran = false;
-            if constexpr (L == Loop::serve_pair) {
-                if (ew) {
-                    const int te = serve_pair_tile_elems(geo.HWs, geo.W);  // a tile: [pad][HWs][pad] cells of 4 planes
-                    fused_serve_pair<T>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done,
-                                        *pre, *sp, ew == 2);
-                    ran = true;
-                }
-            } else if (ew) {
-                fused_serve_xyd<T>(geo, cf, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, *pre, ew == 2);
-                ran = true;
-            }
-            if (!ran)
-                fused_fast_xyd_soa<T, false, true>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target,
-                                                   dvl, done, nullptr, nullptr, 0, pre);
-        } else if constexpr (MODEL == MGDP_MODEL_XYD && CPT > 1) {
-            if (k_target < 0) fused_fast_xyd_soa_xn<T, SLIP, true, CPT>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-            else fused_fast_xyd_soa_xn<T, SLIP, false, CPT>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        } else if constexpr (MODEL == MGDP_MODEL_XYD) {
-            if (SERVED || k_target < 0)
-                fused_fast_xyd_soa<T, SLIP, true>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl,
-                                                  done, nullptr, nullptr, 0, pre);
-            else fused_fast_xyd_soa<T, SLIP, false>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done);
-        } else {
-            // batched grids: the special-first thread -> cell map (dk_class_perm) in the unused pi region
-            uint8_t *perm = (MGDP_DK_PERM && !SERVED && 2 * geo.HW + 16 + 128 <= LY.pi_bytes)
-                                ? reinterpret_cast<uint8_t *>(pis) : nullptr;
-            if (SERVED || k_target < 0)
-                fused_fast_dk_soa<T, true>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done,
-                                           nullptr, nullptr, 0, pre, perm);
-            else fused_fast_dk_soa<T, false>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done,
-                                             nullptr, nullptr, 0, nullptr, perm);
-        }
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
-        return true;  // V and pi were written by their owner threads
-    }
-    if constexpr (SERVED || SOA_ONLY) return true;
-    else {
-    if (fast && MODEL == MGDP_MODEL_XYD && geo.pair) {
-        int vf = 0;
-        if (k_target < 0) fused_fast_xyd2<T, SLIP, true>(geo, cf, cl, V0, pis, slots, flags, k, k_target, vf, dvl, done);
-        else fused_fast_xyd2<T, SLIP, false>(geo, cf, cl, V0, pis, slots, flags, k, k_target, vf, dvl, done);
-        Vfinal = V0 + vf * geo.S;
-    } else if (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL && geo.quad && 4 * geo.HW <= (int)blockDim.x) {
-        if (k_target < 0) fused_quad_xyd<T, SLIP, true>(geo, cf, cl, V0, V1, pis, slots, flags, k, k_target, cur, dvl, done);
-        else fused_quad_xyd<T, SLIP, false>(geo, cf, cl, V0, V1, pis, slots, flags, k, k_target, cur, dvl, done);
+            MGDP_BY_RULE(own,
+                         fused_dk_rows<T, OWN_RULE>(geo, cf, cl2, tiles, slots2, smem + 256, smem + 320, V + vb, V + vb, pi + vb,
+                                                         k, k_target, dvl, done, tl));
     } else {
-        while (true) {
-            const T *Vin = cur ? V1 : V0;
-            T *Vout = cur ? V0 : V1;
-            diff = sweep_lds<T, MODEL, SLIP, MAP, true, MAP == MGDP_MAP_SA>(geo, cf, cl, Vin, Vout, pis);
-            cur ^= 1;
-            ++k;
-            if (k_target < 0) {
-                const bool more = block_any(diff >= cf.tol, flags, parity);
-                parity ^= 1;
-                if (!more || k >= geo.max_sweeps) break;
-            } else {
-                __syncthreads();
-                if (k >= k_target) break;
-            }
+        // The layout of smem_layout: Loop::wave, the direction-major loops (one thread per cell, or CPT
+        // cells: xyd_pair2 / xyd_x2 / xyd_x4) and, for Loop::generic alone, the cell-major paths.
+        constexpr bool SOA_ONLY = loop_is_soa_only(L);
+        constexpr int CPT = L == Loop::xyd_pair2 || L == Loop::xyd_x2 ? 2 : (L == Loop::xyd_x4 ? 4 : 1);
+        const bool fast = MAP == MGDP_MAP_CELL && geo.HW <= CPT * (int)blockDim.x;
+        const bool soa = SOA_ONLY || (fast && !geo.pair && !geo.quad);
+        if (!SERVED) copy16(cl, cells + (long long)e * geo.HWp, geo.HWp);
+        if (!soa) {
+            // cell-major paths use the first S entries of each (Ss-sized) tile
+            if (k == 0) zero16(V0, geo.S * (int)sizeof(T));
+            else copy16(V0, V + vb, geo.S * (int)sizeof(T));
         }
-        dvl = (double)block_max(diff, slots, 0);
-        done(k, dvl);
-        if (MAP == MGDP_MAP_CELL) {  // pi of the last sweep = argmax on V_{k-1}
-            sweep_lds<T, MODEL, SLIP, MAP, false, true>(geo, cf, cl, cur ? V0 : V1, nullptr, pis);
+        // the served pair loop's fresh start needs no stage here: it clears its flag bytes once per grid and
+        // sets its first pair's in its own first stage (fused_serve_pair)
+        bool own_start = false;
+        if constexpr (L == Loop::serve_pair) own_start = sc->ew != 0 && k == 0;
+        if (!own_start) {
+            if (threadIdx.x < 64) flags[threadIdx.x] = 0;
             __syncthreads();
         }
+        // Irregular: a served solve is always own-rule, so Loop::wave and the one-thread-per-cell loops the
+        // server also runs pick the own-rule instantiation by SERVED || own
+        if constexpr (L == Loop::wave) {  // lone XYD grid on one wave, N cells per lane (host: B == 1, blockDim 64)
+            static_assert(MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL, "one-wave path is XYD, cell mapping");
+            MGDP_BY_RULE(SERVED || own,
+                         fused_wave_xyd<T, SLIP, OWN_RULE, N>(geo, cf, cl, V0, V1, V + vb, V + vb, pi + vb, k, k_target, dvl, done));
+        } else if constexpr (L == Loop::xyd_pair2) {
+            static_assert(MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "pair path: plain XYD");
+            MGDP_BY_RULE(own,
+                         fused_pair_xyd<T, OWN_RULE, 128 * N>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done));
+        } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && L == Loop::dk_half) {
+            MGDP_BY_RULE(own,
+                         fused_dk_half<T, OWN_RULE, 64 * N>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done));
+        } else if constexpr (MODEL == MGDP_MODEL_DOORKEY && L == Loop::dk_1t) {
+            MGDP_BY_RULE(own,
+                         fused_fast_dk_1t<T, OWN_RULE>(geo, cf, cl, V0, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done));
+        } else if constexpr (loop_is_serve_ew(L)) {
+            static_assert(SERVED && MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "served plain XYD grid");
+            if (sc->ew != 0) {
+                if constexpr (L == Loop::serve_pair) {
+                    const int te = serve_pair_tile_elems(geo.HWs, geo.W);  // a tile: [pad][HWs][pad] cells of 4 planes
+                    fused_serve_pair<T>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, sc->topo, sc->sp,
+                                        sc->ew == 2);
+                } else {
+                    fused_serve_xyd<T>(geo, cf, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, sc->topo, sc->ew == 2);
+                }
+            } else {  // this grid's wave edges do not allow the served loop: the general one
+                fused_fast_xyd_soa<T, false, true>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done,
+                                                   nullptr, nullptr, 0, &sc->topo);
+            }
+        } else if constexpr (MODEL == MGDP_MODEL_XYD && CPT > 1) {
+            MGDP_BY_RULE(own,
+                         fused_fast_xyd_soa_xn<T, SLIP, OWN_RULE, CPT>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target,
+                                                             dvl, done));
+        } else if (SERVED || soa) {  // served lone grids are always on this path (serve_eligible)
+            if constexpr (MODEL == MGDP_MODEL_XYD) {
+                MGDP_BY_RULE(SERVED || own,
+                             fused_fast_xyd_soa<T, SLIP, OWN_RULE>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl,
+                                                         done, nullptr, nullptr, 0, sc ? &sc->topo : nullptr));
+            } else {
+                // batched grids: the special-first thread -> cell map (dk_class_perm) in the unused pi region
+                // (tried: thread t on cell t, DESIGN.md 11.2 -- slower)
+                uint8_t *perm = (!SERVED && 2 * geo.HW + 16 + 128 <= LY.pi_bytes) ? reinterpret_cast<uint8_t *>(pis) : nullptr;
+                MGDP_BY_RULE(SERVED || own,
+                             fused_fast_dk_soa<T, OWN_RULE>(geo, cf, cl, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, k_target, dvl, done,
+                                                  nullptr, nullptr, 0, sc ? &sc->topo : nullptr, perm));
+            }
+        } else if constexpr (!SERVED && !SOA_ONLY) {
+            // The cell-major paths of Loop::generic (launches only): the pair and quad loops, else one
+            // sweep_lds per iteration on two LDS tiles; V and pi leave through LDS.  (Tried as a function
+            // of its own: one SGPR moved in the seven kernels that run it, so it stays in place.)
+            int cur = 0;
+            const T *Vfinal = nullptr;
+            if (fast && MODEL == MGDP_MODEL_XYD && geo.pair) {
+                int vf = 0;
+                MGDP_BY_RULE(own, fused_fast_xyd2<T, SLIP, OWN_RULE>(geo, cf, cl, V0, pis, slots, flags, k, k_target, vf, dvl,
+                                                                    done));
+                Vfinal = V0 + vf * geo.S;
+            } else if (MODEL == MGDP_MODEL_XYD && MAP == MGDP_MAP_CELL && geo.quad && 4 * geo.HW <= (int)blockDim.x) {
+                MGDP_BY_RULE(own, fused_quad_xyd<T, SLIP, OWN_RULE>(geo, cf, cl, V0, V1, pis, slots, flags, k, k_target, cur,
+                                                                   dvl, done));
+            } else {
+                int parity = 0;
+                T diff = (T)0;
+                while (true) {
+                    const T *Vin = cur ? V1 : V0;
+                    T *Vout = cur ? V0 : V1;
+                    diff = sweep_lds<T, MODEL, SLIP, MAP, true, MAP == MGDP_MAP_SA>(geo, cf, cl, Vin, Vout, pis);
+                    cur ^= 1;
+                    ++k;
+                    if (own) {
+                        const bool more = block_any(diff >= cf.tol, flags, parity);
+                        parity ^= 1;
+                        if (!more || k >= geo.max_sweeps) break;
+                    } else {
+                        __syncthreads();
+                        if (k >= k_target) break;
+                    }
+                }
+                dvl = (double)block_max(diff, slots, 0);
+                done(k, dvl);
+                if (MAP == MGDP_MAP_CELL) {  // pi of the last sweep = argmax on V_{k-1}
+                    sweep_lds<T, MODEL, SLIP, MAP, false, true>(geo, cf, cl, cur ? V0 : V1, nullptr, pis);
+                    __syncthreads();
+                }
+            }
+            copy16(V + vb, Vfinal ? Vfinal : (cur ? V1 : V0), geo.S * (int)sizeof(T));
+            copy_pi(pi + vb, pis, geo.S);
+        }
     }
-    copy16(V + vb, Vfinal ? Vfinal : (cur ? V1 : V0), geo.S * (int)sizeof(T));
-    copy_pi(pi + vb, pis, geo.S);
-    if (threadIdx.x == 0) {
-        kenv[e] = k;
-        if (geo.kexec) geo.kexec[e] = k;
-        dvenv[e] = dvl;
-    }
+    record_grid(geo, kenv, dvenv, e, k, dvl, writer());
     return true;
-    }
 }
+#undef MGDP_BY_RULE
 
 // Loop::wave: the one-wave lone-grid variant (fused_wave_xyd), 64 threads, so its N cells per lane
 // may use the whole register file.
@@ -464,8 +395,7 @@ vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__res
     const bool work = fused_grid<T, MODEL, SLIP, MAP, false, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, k_target,
                                                                  fresh, lone, epoch,
                                                                  geo.order ? (int)geo.order[blockIdx.x] : (int)blockIdx.x,
-                                                                 k, dvl, nullptr,
-                                                                 kOwnLds ? gk : nullptr);
+                                                                 k, dvl, kOwnLds ? gk : nullptr);
     // a launch-wide-rule launch (wave2 with gk) reduces and publishes through its own counter tree
     const bool gk_pub = kOwnLds && gk != nullptr && k_target < 0 && !k_target_dev;
     if (in_kernel_reduce && !gk_pub)
@@ -555,18 +485,16 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
     unsigned long long t_seen = t_start, busy = 0, solves = 0;
     __syncthreads();
     // the grid stays put between kServeNewCells requests: resolve this thread's cell topology once
-    typename TopoOf<T, MODEL>::type topo;
-    ServePairTopo<T> sp = {};  // Loop::serve_pair: its own per-grid constants
-    int ew = 0;  // Loop::serve_ew: 0 = the grid falls back, 1 = fused_serve_xyd, 2 = the same, tiles to clear
+    ServeCtx<T, MODEL> sc = {};
     __shared__ int s_ew;
     auto resolve = [&]() {
         if constexpr (L == Loop::generic || loop_is_serve_ew(L)) {
             const int cc = (int)threadIdx.x < geo.HW ? (int)threadIdx.x : 0;
-            if constexpr (MODEL == MGDP_MODEL_XYD) topo = xyd_topo_soa<T>(cl, geo, cc);
-            else topo = dk_topo_soa(cl, geo, cc);
+            if constexpr (MODEL == MGDP_MODEL_XYD) sc.topo = xyd_topo_soa<T>(cl, geo, cc);
+            else sc.topo = dk_topo_soa(cl, geo, cc);
         }
-        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) sp = serve_pair_topo<T>(cl, geo, cf, topo, (int)threadIdx.x);
-        if constexpr (loop_is_serve_ew(L)) ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
+        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) sc.sp = serve_pair_topo<T>(cl, geo, cf, sc.topo, (int)threadIdx.x);
+        if constexpr (loop_is_serve_ew(L)) sc.ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
     };
     resolve();
     while (true) {
@@ -629,12 +557,10 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
         int k;
         double dvl;
         if (!fused_grid<T, MODEL, SLIP, MAP, true, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, -1, 1, true,
-                                                   (unsigned int)cmd, 0, k, dvl,
-                                                   (L == Loop::generic || loop_is_serve_ew(L)) ? &topo : nullptr, nullptr, ew,
-                                                   &sp) &&
+                                                   (unsigned int)cmd, 0, k, dvl, nullptr, &sc) &&
             threadIdx.x == 0)
             publish_tagged(host_out, k, dvl, (unsigned int)cmd);
-        if (ew == 2) ew = 1;  // the tiles' pads stay +0 until the next grid
+        if (sc.ew == 2) sc.ew = 1;  // the tiles' pads stay +0 until the next grid
         served = cmd;
         t_last = __builtin_amdgcn_s_memrealtime();
         if (threadIdx.x == 0) {
@@ -700,19 +626,10 @@ __host__ __device__ constexpr int bserve_min_waves(int P) {
     return sizeof(T) == 4 ? (P <= 2 ? 8 : P <= 4 ? 5 : P <= 6 ? 4 : 3)
                           : (P == 1 ? 8 : P == 2 ? 5 : P == 3 ? 4 : P == 4 ? 3 : P <= 7 ? 2 : 1);
 }
-#ifndef MGDP_BSERVE_MINW  // A/B builds: 0 = the compiler's choice (wave2_min_waves)
-#define MGDP_BSERVE_MINW 1
-#endif
-#ifndef MGDP_BSERVE_PRIO  // A/B builds: 0 = no s_setprio (polling waves at the solving waves' priority)
-#define MGDP_BSERVE_PRIO 1
-#endif
-#ifndef MGDP_BSERVE_OPQ  // A/B builds: 0 = the lane index as threadIdx.x in the request loop's solve
-#define MGDP_BSERVE_OPQ 1
-#endif
 // MULTI: the launch has fewer workgroups than grids (a batch past the resident capacity, MGDP_BSERVE=2):
 // its own instantiation, so the resident loop keeps its registers.
 template <typename T, int P, bool MULTI = false>
-__global__ void __launch_bounds__(64, MGDP_BSERVE_MINW ? bserve_min_waves<T>(P) : wave2_min_waves<T>(Loop::wave2, P))
+__global__ void __launch_bounds__(64, bserve_min_waves<T>(P))
 vi_bserve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__restrict__ V,
                  int8_t *__restrict__ pi, int32_t *__restrict__ kenv, double *__restrict__ dvenv,
                  unsigned long long *__restrict__ host_out, const unsigned long long *__restrict__ host_cmd,
@@ -740,7 +657,7 @@ vi_bserve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__re
     const long long vb = (long long)e * geo.S;
     while (true) {
         unsigned long long cmd;
-        if (MGDP_BSERVE_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);  // polling: the waves still sweeping get the issue slots
         if (fwd) {
             unsigned long long c = served;
             // Host polls are PCIe reads the forwarder keeps in flight (up to 24, LDS DMA); while other grids
@@ -795,11 +712,9 @@ vi_bserve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__re
             cmd = (dw & kBreqQuit) ? kServeQuit : ((dw & 0xffffffffull) | (dw & kServeLast));
         }
         if (cmd == kServeQuit) break;
-        if (MGDP_BSERVE_PRIO) {
-            // the first prio_n workgroups hold the dispatch order's longest grids (MGDP_BSERVE_PRIO_FRAC)
-            if ((int)blockIdx.x < prio_n) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(1);
-        }
+        // the first prio_n workgroups hold the dispatch order's longest grids (MGDP_BSERVE_PRIO_FRAC)
+        if ((int)blockIdx.x < prio_n) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(1);
         const unsigned long long t_seen = __builtin_amdgcn_s_memrealtime();
         int k = 0;
         double dvl = 0.0;
@@ -819,42 +734,33 @@ vi_bserve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__re
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // one wave: the cells are in place
                 int kg = 0;
                 double dg = 0.0;
-                fused_wave2_xyd<T, true, P, true, (bool)MGDP_BSERVE_OPQ>(geo, cf, cl, tile, V + vg, V + vg, pi + vg, kg, -1,
-                                                                        dg, done, GkCtx{});
-                if (lane == 0) {
-                    kenv[eg] = kg;
-                    if (geo.kexec) geo.kexec[eg] = kg;
-                    dvenv[eg] = dg;
-#ifdef MGDP_BSERVE_DEBUG_WG  // diagnostics build: which workgroup and iteration solved each grid
-                    if (geo.kexec) geo.kexec[eg] = (int)blockIdx.x | (((i - (int)blockIdx.x) / (int)gridDim.x) << 20);
-#endif
-                }
+                fused_wave2_xyd<T, true, P, true, true>(geo, cf, cl, tile, V + vg, V + vg, pi + vg, kg, -1, dg, done,
+                                                        GkCtx{});
+                record_grid(geo, kenv, dvenv, eg, kg, dg, lane == 0);
                 kmn = min(kmn, kg);
                 kmx = max(kmx, kg);
                 dvm = dg > dvm ? dg : dvm;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             gk_exit<true>(GkCtx{gk, (unsigned int)cmd, (int)blockIdx.x, (int)gridDim.x, host_out}, kmx, dvm,
-                          MGDP_BSERVE_OPQ ? late_tid(0) : lane, kmn);
+                          late_tid(0), kmn);
             k = kmx;
         } else {
-            fused_wave2_xyd<T, true, P, true, (bool)MGDP_BSERVE_OPQ>(geo, cf, cl, tile, V + vb, V + vb, pi + vb, k, -1, dvl,
-                                                                    done, GkCtx{gk, (unsigned int)cmd, e, geo.B, host_out});
+            fused_wave2_xyd<T, true, P, true, true>(geo, cf, cl, tile, V + vb, V + vb, pi + vb, k, -1, dvl, done,
+                                                    GkCtx{gk, (unsigned int)cmd, e, geo.B, host_out});
         }
-        if (lane == 0 && !multi) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
+        record_grid(geo, kenv, dvenv, e, k, dvl, lane == 0 && !multi);
 #ifdef MGDP_BSERVE_TRACE  // trace build: this grid's start / end after the forwarder saw the request,
                           // 10 ns ticks in the low / high 16 bits of its executed-sweeps word
+        if (lane == 0 && !multi) {
             const unsigned long long t0 = __hip_atomic_load(breq + (blockIdx.x % (unsigned)copies) * 16u + 1,
                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
             const unsigned long long a = t_seen - t0 < 0xffffull ? t_seen - t0 : 0xffffull;
             const unsigned long long b = t1 - t0 < 0xffffull ? t1 - t0 : 0xffffull;
             if (geo.kexec) geo.kexec[e] = (int)(a | (b << 16));
-#endif
         }
+#endif
         served = cmd;
         t_last = __builtin_amdgcn_s_memrealtime();
         busy += t_last - t_seen;
@@ -914,23 +820,19 @@ vi_fused_opts_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *
     const int e = blockIdx.x;
     int k = fresh ? 0 : kenv[e];
     double dvl = fresh ? 0.0 : dvenv[e];
-    // fixed-point completion (fused_grid); not for a finite horizon, whose sweeps depend on the step
-    if (HMODE == 0 && k_target > k && k > 0 && dvl == 0.0) {
+    // fixed-point completion; not for a finite horizon, whose sweeps depend on the step
+    if (HMODE == 0 && grid_complete_at(k, dvl, k_target)) {
         if (threadIdx.x == 0) kenv[e] = k_target;
         k = k_target;
     }
-    const bool work = k_target < 0 ? (!(k > 0 && dvl < geo.tol) && k < geo.max_sweeps) : (k < k_target);
+    const bool work = grid_has_work(geo, k, dvl, k_target);
     const bool lone = in_kernel_reduce && gridDim.x == 1;
     if (work) {
         const long long vb = (long long)e * geo.S;
         copy16(cl, cells + (long long)e * geo.HWp, geo.HWp);
         if (threadIdx.x < 64) flags[threadIdx.x] = 0;
         __syncthreads();
-        auto done = [&](int kk, double dv) {
-            if (lone && threadIdx.x == 0)
-                publish(host_out, (unsigned long long)kk, (unsigned long long)__double_as_longlong(dv),
-                        (unsigned long long)kk, epoch);
-        };
+        auto done = [&](int kk, double dv) { publish_solve<false>(host_out, kk, dv, epoch, lone, threadIdx.x == 0); };
         int8_t *pit = HMODE == 2 ? pi_t + vb : nullptr;
         const long long pstride = (long long)geo.B * geo.S;
         if constexpr (MODEL == MGDP_MODEL_XYD) {
@@ -958,11 +860,7 @@ vi_fused_opts_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *
                                                    k_target, dvl, done, rgoal, pit, pstride);
             }
         }
-        if (threadIdx.x == 0) {
-            kenv[e] = k;
-            if (geo.kexec) geo.kexec[e] = k;
-            dvenv[e] = dvl;
-        }
+        record_grid(geo, kenv, dvenv, e, k, dvl, threadIdx.x == 0);
     }
     if (in_kernel_reduce)
         fused_reduce(red, ticket, host_out, k, dvl, reinterpret_cast<unsigned int *>(slots + 16), epoch, work,
@@ -1246,29 +1144,18 @@ struct PipeRow {
 
 // V is streamed once per sweep (Vin read, Vout written; the next sweep's Vin is the whole
 // 553 MB array again, far past the 256 MB MALL), so the loads and stores are nontemporal:
-// bit 0 stores, bit 1 loads.  Measured on empty16x65536 (profiles/r01_sweep_nt/): 107.8 µs
-// plain, 101.5 µs stores only, 98.0 µs both.
-#ifndef MGDP_SWEEP_NT
-#define MGDP_SWEEP_NT 3
-#endif
+// measured on empty16x65536 (profiles/r01_sweep_nt/): 107.8 µs plain, 101.5 µs stores only, 98.0 µs both.
 template <typename T>
 __device__ __forceinline__ void st_v4(V4<T> *dst, const V4<T> &v) {
-    if (MGDP_SWEEP_NT & 1) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v.v[j], &dst->v[j]);
-    } else {
-        *dst = v;
-    }
+    for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(v.v[j], &dst->v[j]);
 }
 template <typename T>
 __device__ __forceinline__ V4<T> ld_v4(const V4<T> *src) {
-    if (MGDP_SWEEP_NT & 2) {
-        V4<T> v;
+    V4<T> v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v.v[j] = __builtin_nontemporal_load(&src->v[j]);
-        return v;
-    }
-    return *src;
+    for (int j = 0; j < 4; ++j) v.v[j] = __builtin_nontemporal_load(&src->v[j]);
+    return v;
 }
 
 template <typename T, int MODEL, bool SLIP, int DEPTH>

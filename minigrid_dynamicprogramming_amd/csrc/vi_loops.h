@@ -5,15 +5,6 @@
 // vi_kernels.h); see vi.hip for the DP semantics and the data layout.
 #pragma once
 
-// MGDP_RUNTO_DV_ALL=1 (A/B builds): k_target loops compute |dV| on every sweep, not only the last.
-// MGDP_DK_DEAD=0 (A/B builds): batched DoorKey waves of absorbing cells only do the full sweep.
-#ifndef MGDP_DK_DEAD
-#define MGDP_DK_DEAD 1
-#endif
-#ifndef MGDP_RUNTO_DV_ALL
-#define MGDP_RUNTO_DV_ALL 0
-#endif
-
 namespace mgdp {
 // ------------------------------------------------------------------------------------------------
 // (state, action) lane mapping: 8 lanes per state, lane a evaluates action a, a wave shuffle
@@ -209,13 +200,10 @@ __device__ __forceinline__ void publish_tagged(unsigned long long *host_out, int
 // (profiles/r05_wt/): a resident batch's kernel 1-2 % shorter (FourRooms x 4096 45.0 -> 44.0 us,
 // LavaS11N5 x 8192 27.5 -> 27.1), a batch past residency 6 % longer (the waves queued behind the
 // write-through stores): fused_wave2_xyd writes through in the launches with the in-launch reduction
-// (resident batches), its own instantiation.  MGDP_WT_EXIT=0 (A/B builds): never.
-#ifndef MGDP_WT_EXIT
-#define MGDP_WT_EXIT 1
-#endif
+// (resident batches), its own instantiation.
 template <typename T>
 __device__ __forceinline__ void store_v4_exit(T *p, const V4<T> &v, bool wt) {
-    if (MGDP_WT_EXIT && wt) {
+    if (wt) {
         unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
         if constexpr (sizeof(T) == 4) {
             // one 16-B store, as the plain form (two 8-B atomic stores re-paired the loop's registers:
@@ -239,7 +227,7 @@ __device__ __forceinline__ void store_v4_exit(T *p, const V4<T> &v, bool wt) {
     }
 }
 __device__ __forceinline__ void store_pi_exit(int8_t *p, uint32_t pk, bool wt) {
-    if (MGDP_WT_EXIT && wt)
+    if (wt)
         __hip_atomic_store(reinterpret_cast<uint32_t *>(p), pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else
         *reinterpret_cast<uint32_t *>(p) = pk;
@@ -1264,36 +1252,13 @@ __device__ __forceinline__ void gk_exit(const GkCtx &g, int k_rep, double dv, in
     }
 }
 
-#ifndef MGDP_WAVE2_PREFETCH  // A/B builds: 1 = fused_wave2_xyd reads the next sweep's fronts early
-#define MGDP_WAVE2_PREFETCH 0   // measured neutral (profiles/r05_pf/) and +9 VGPRs at P = 4
-#endif
-#ifndef MGDP_WAVE2_PK  // A/B builds: 1 = fused_wave2_xyd's multiplies and |dV| differences as packed fp32 pairs
-#define MGDP_WAVE2_PK 0
-#endif
-#ifndef MGDP_WAVE2_DVTREE  // A/B builds: 1 = fused_wave2_xyd folds |dV| as a v_max3 tree
-#define MGDP_WAVE2_DVTREE 0   // measured neutral (profiles/r05_tree/) and +9 VGPRs at P = 2, 4 (81 -> 90: 6 -> 5 waves)
-#endif
-// max of |x_i| over N values as a tree of v_max3 (depth log3 N instead of a running max's N / 2:
-// max is exact and order-free, so the result is the same bits)
-template <int N, typename T>
-__device__ __forceinline__ T tree_max3(const T *x) {
-    if constexpr (N == 1) {
-        return x[0];
-    } else if constexpr (N == 2) {
-        return vmax(x[0], x[1]);
-    } else if constexpr (N == 3) {
-        return vmax(vmax(x[0], x[1]), x[2]);
-    } else {
-        constexpr int M = (N + 2) / 3;
-        T y[M];
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            const int a = 3 * i;
-            y[i] = a + 2 < N ? vmax(vmax(x[a], x[a + 1]), x[a + 2]) : (a + 1 < N ? vmax(x[a], x[a + 1]) : x[a]);
-        }
-        return tree_max3<M, T>(y);
-    }
-}
+// fused_wave2_xyd, tried and measured, not kept:
+//  * reading the next sweep's fronts right after a sweep's own stores (so the LDS round trip overlaps the
+//    |dV| reduction and stop ballot): neutral (profiles/r05_pf/) and +9 VGPRs at P = 4;
+//  * the multiplies and |dV| differences as packed fp32 pairs (v_pk_mul_f32 / v_pk_add_f32): slower
+//    ("Packed fp32 in the one-wave batch loop");
+//  * the |dV| fold as a v_max3 tree: neutral (profiles/r05_tree/) and +9 VGPRs at P = 2, 4 (81 -> 90:
+//    6 -> 5 waves).
 template <int B> struct WaveBuf { static constexpr int value = B; };
 // WT: write the exit stores through the L2 (store_v4_exit; the caller instantiates it for the launches
 // with the in-launch reduction, i.e. resident batches)
@@ -1342,25 +1307,16 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
     for (int j = 0; j < P; ++j)
         goal_blocks |= (__builtin_amdgcn_ballot_w64(((goal >> (4 * j)) & 15u) != 0u) != 0ull ? 1u : 0u) << j;
     T diff = (T)0;
-    // The north / south fronts of the sweep about to run.  With MGDP_WAVE2_PREFETCH a sweep reads the
-    // next sweep's right after storing its own planes, so the LDS round trip overlaps its |dV|
-    // reduction, stop ballot and branch instead of opening the next sweep (the reads of a sweep
-    // that turns out to be the last are simply unused).
-    T FS[P], FN[P];
-    auto read_fronts = [&]() {
+    // One sweep in -> out; returns whether another follows (the caller ran at least one: fused_grid
+    // only calls with work to do).  The stop test ends the sweep that decides it, so at an exit the
+    // sweep's own operands are V_{k-1} (in) and V_k (out) -- no loop-carried copy of V_{k-1}.
+    auto sweep = [&](const T (&in)[P][4], T (&out)[P][4]) -> bool {
+        T FS[P], FN[P], R[P], L[P];  // the sweep's north / south fronts (LDS), east / west (DPP)
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             FS[j] = S1[j * 64 + lane + W];
             FN[j] = N3[j * 64 + lane - W];
         }
-    };
-    if (MGDP_WAVE2_PREFETCH) read_fronts();
-    // One sweep in -> out; returns whether another follows (the caller ran at least one: fused_grid
-    // only calls with work to do).  The stop test ends the sweep that decides it, so at an exit the
-    // sweep's own operands are V_{k-1} (in) and V_k (out) -- no loop-carried copy of V_{k-1}.
-    auto sweep = [&](const T (&in)[P][4], T (&out)[P][4]) -> bool {
-        if (!MGDP_WAVE2_PREFETCH) read_fronts();
-        T R[P], L[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             R[j] = dpp_mov<0x134>(in[j][0]);  // wave_rol:1 -- lane i gets lane (i+1) mod 64
@@ -1375,18 +1331,8 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
             const T m02 = vmax(in[j][0], in[j][2]), m13 = vmax(in[j][1], in[j][3]);
             const T m[4] = {vmax(vmax(in[j][0], m13), FE), vmax(vmax(in[j][1], m02), FS[j]),
                             vmax(vmax(in[j][2], m13), FW), vmax(vmax(in[j][3], m02), FN[j])};
-            if constexpr (MGDP_WAVE2_PK && sizeof(T) == 4) {  // two packed multiplies (v_pk_mul_f32)
-                typedef float f2 __attribute__((ext_vector_type(2)));
-                const f2 g2 = {ge[j], ge[j]};
-                const f2 a = f2{m[0], m[1]} * g2, b = f2{m[2], m[3]} * g2;
-                o[j][0] = a.x;
-                o[j][1] = a.y;
-                o[j][2] = b.x;
-                o[j][3] = b.y;
-            } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) o[j][q] = ge[j] * m[q];
-            }
+            for (int q = 0; q < 4; ++q) o[j][q] = ge[j] * m[q];
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -1401,31 +1347,12 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
             N3[j * 64 + lane] = o[j][3];
         }
         asm volatile("" ::: "memory");
-        if (MGDP_WAVE2_PREFETCH) read_fronts();  // LDS is in order per wave: after this sweep's stores
         // a k_target loop reports |dV| of its last sweep only (a uniform branch)
-        if (LOCAL || MGDP_RUNTO_DV_ALL || k + 1 == k_target) {
-            if (MGDP_WAVE2_DVTREE) {
-                T ad[4 * P];
+        if (LOCAL || k + 1 == k_target) {
 #pragma unroll
-                for (int j = 0; j < P; ++j)
+            for (int j = 0; j < P; ++j)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) ad[4 * j + q] = vabs(o[j][q] - in[j][q]);
-                dm = tree_max3<4 * P, T>(ad);
-            } else if constexpr (MGDP_WAVE2_PK && sizeof(T) == 4) {  // packed differences (v_pk_add_f32)
-                typedef float f2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                for (int j = 0; j < P; ++j) {
-                    const f2 a = f2{o[j][0], o[j][1]} - f2{in[j][0], in[j][1]};
-                    const f2 b = f2{o[j][2], o[j][3]} - f2{in[j][2], in[j][3]};
-                    dm = vmax(vmax(dm, vabs(a.x)), vabs(a.y));
-                    dm = vmax(vmax(dm, vabs(b.x)), vabs(b.y));
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < P; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dm = vmax(dm, vabs(o[j][q] - in[j][q]));
-            }
+                for (int q = 0; q < 4; ++q) dm = vmax(dm, vabs(o[j][q] - in[j][q]));
         }
         diff = dm;
 #pragma unroll
@@ -1587,7 +1514,7 @@ __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf
             }
         }
         T dm = (T)0;
-        if (LOCAL || MGDP_RUNTO_DV_ALL || k + 1 == k_target) {  // a k_target loop: |dV| of its last sweep only
+        if (LOCAL || k + 1 == k_target) {  // a k_target loop: |dV| of its last sweep only
 #pragma unroll
             for (int j = 0; j < HB; ++j)
 #pragma unroll
@@ -1758,7 +1685,7 @@ __device__ __forceinline__ void fused_wave2n_xyd(const Geo &geo, const Coef<T> &
         }
         if (w == 1 && lane == 0) edge[2 * (b ^ 1)] = o[0][0];
         if (w == 0 && lane == 63) edge[2 * (b ^ 1) + 1] = o[PW - 1][2];
-        if (LOCAL || MGDP_RUNTO_DV_ALL || k + 1 == k_target) {
+        if (LOCAL || k + 1 == k_target) {
 #pragma unroll
             for (int j = 0; j < PW; ++j)
 #pragma unroll
@@ -2007,7 +1934,7 @@ __device__ __forceinline__ void fused_fast_dk_soa(const Geo &geo, const Coef<T> 
     // is +0 in both tiles and stays +0 (dk_step_fast yields exactly +0 there), so its value sweeps
     // store +0 with no arithmetic and no front reads.  The special-first map packs a DoorKey-16
     // grid's absorbing cells into its fourth wave.
-    const bool wdead = MGDP_DK_DEAD && __builtin_amdgcn_ballot_w64(tp.walk != 0u) == 0ull;
+    const bool wdead = __builtin_amdgcn_ballot_w64(tp.walk != 0u) == 0ull;
     T own[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -2035,7 +1962,7 @@ __device__ __forceinline__ void fused_fast_dk_soa(const Geo &geo, const Coef<T> 
 #pragma unroll
             for (int q = 0; q < 4; ++q) nbs[q] = *reinterpret_cast<const V4<T> *>(Vin + tpf.nb[q]);
             // a k_target loop reports |dV| of its last sweep only: the others skip the differences
-            if (LOCAL || MGDP_RUNTO_DV_ALL || k + 1 == k_target) {
+            if (LOCAL || k + 1 == k_target) {
                 if (wcls == 0u) d = dk_step_fast<T, HMODE != 0, false, false>(tpf, cf, in, nbs, outv, rg);
                 else if (wcls == 1u) d = dk_step_fast<T, HMODE != 0, true, false>(tpf, cf, in, nbs, outv, rg);
                 else d = dk_step_fast<T, HMODE != 0, true, true>(tpf, cf, in, nbs, outv, rg);

@@ -318,6 +318,7 @@ def test_idle_exit_and_relaunch(dtype, monkeypatch):
     ("8x8", "serve_wave", ()),                  # the one-wave served loop
     ("doorkey8", "serve_dk_half", ()),          # DoorKey, states over two threads
     ("doorkey16", "serve", (("MGDP_DK_HALF", "0"),)),  # DoorKey on the generic server
+    ("16x16", "serve", (("MGDP_LONE_CPT", "2"),)),  # two cells per thread (Loop::xyd_x2: 128 threads, tests/test_vi_plan.py)
 ])
 def test_other_served_loops_through_the_shared_entry(name, variant, env, dtype, monkeypatch):
     """Two plain solves on one launch on each of the other loops vi_serve_kernel is instantiated for."""

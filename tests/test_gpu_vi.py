@@ -312,6 +312,27 @@ def test_fused_doorkey_lone_and_batched_bit_exact(persistent, dtype, one_tile, m
             np.testing.assert_array_equal(r.pi, o["pi"])
 
 
+def test_dk_1t_run_to_continues_resumed_grids(monkeypatch):
+    """The one-tile DoorKey loop's run-to instantiation on grids resumed from HBM (the solves above end at
+    exact fixed points, which need no second launch): a fresh run_to(5), then on to the oracle's K; the
+    sweep count, dV, V and pi bit for bit."""
+    monkeypatch.setenv("MGDP_DK_1T", "1")
+    cells = np.stack([cells_from_enc(e) for e in load("grids_doorkey16.npz")["enc"][:3]])
+    o = oracle.value_iteration(1, cells, dtype="f32")
+    vi = mg.ValueIteration(cells, model="doorkey", dtype="f32")
+    try:
+        assert vi.variant == "dk_1t"
+        vi.reset()
+        vi.run_to(5)
+        dv = vi.run_to(o["sweeps"])
+        vi.finish(o["sweeps"], dv)
+        assert vi.sweeps == o["sweeps"] and dv == o["dv"]
+        np.testing.assert_array_equal(vi.values(), o["V"])
+        np.testing.assert_array_equal(vi.policy(), o["pi"])
+    finally:
+        vi.close()
+
+
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_tolerance_threshold_edges(dtype):
     """The kernels test |dV| >= tol against tol rounded up to the value type; exact for tolerances

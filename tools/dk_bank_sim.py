@@ -3,7 +3,7 @@ ds_read_b128 = 4 groups of 16 lanes {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... o
 ds_write_b128 = 8 groups of 8 contiguous lanes on (a/4) mod 32; each extra distinct address on a
 busy 16-B slot of a group costs one LDS cycle).  Per grid-sweep LDS-array cycles of:
   cellperm  fused_fast_dk_soa with the special-first thread -> cell map (round 4's default),
-  identity  fused_fast_dk_soa with thread t on cell t (MGDP_DK_PERM=0),
+  identity  fused_fast_dk_soa with thread t on cell t (tried and measured slower: profiles/r03_dk/perm/),
   rows      fused_dk_rows (whole rows per 16 lanes, planes 1 / 3 only, DPP east / west).
 Grids: tests/golden/grids_doorkey16.npz (reference-generated).  Run: python tools/dk_bank_sim.py"""
 import os
