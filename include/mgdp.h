@@ -343,9 +343,46 @@ int mgdp_envs_step(mgdp_envs *envs, const int32_t *actions, uint8_t *obs, int32_
 int mgdp_envs_step_device(mgdp_envs *envs, const int32_t *d_actions, uint8_t *d_obs,
                           int32_t *d_direction, double *d_reward, uint8_t *d_terminated,
                           uint8_t *d_truncated, int32_t *d_status);
+/* Tabular policies on resident envs (additive entry points, the ABI version is
+ * unchanged).  pi: int8 action lanes in the state order of mgdp_vi_get_policy for `model` on the
+ * handle's W x H -- XYD s = (y*W + x)*4 + dir, lanes = env actions 0..6; DoorKey
+ * s = (((y*W + x)*4 + dir)*2 + has_key)*2 + door_open (has_key: a Key is carried; door_open: the
+ * grid's one Door is open), lanes 0..4 = env actions (0, 1, 2, 3, 5).  T = 1: stationary, [B][S];
+ * T > 1: time-indexed [T][B][S] as mgdp_vi_get_policy_t returns it, the row is the env's step_count
+ * before the step.  Call-level refusals: MGDP_E_INVALID for an unknown model, T < 1 or
+ * trace_len < 0; MGDP_E_UNSUPPORTED once Box contents planes exist (mgdp_envs_set_contents).
+ * Everything else is per env, in status (B): MGDP_E_UNSUPPORTED for a grid or carry outside the
+ * model (XYD: a cell other than empty / wall / floor / goal / lava, or anything carried; DoorKey:
+ * any other cell than those, doors and keys, not exactly one door and one key of its colour on
+ * the grid or carried, or another carried object), MGDP_E_INVALID for step_count outside [0, T) of
+ * a time-indexed policy, MGDP_E_ACTION for a lane outside [0, A) (-1 included), MGDP_E_BOUNDS from
+ * the step; such an env is not stepped, and the call still returns MGDP_OK.
+ *   mgdp_envs_policy_actions*: the env action the policy takes at each env's current state
+ *     (int32, -1 where status != 0), e.g. as the actions of mgdp_envs_step_device.
+ *   mgdp_envs_rollout*: every env runs from its current state (step_count and carry as they are)
+ *     through the step of mgdp_envs_step -- NoDeath and the pickup / toggle cell mutation included,
+ *     no observations -- until it terminates, truncates, fails (status) or has taken n_max steps
+ *     (n_max <= 0: no budget), in one launch.  steps: steps taken; ret: their rewards summed in step
+ *     order from +0.0 (fp64); terminated / truncated: the last step's flags (0 if none was taken).
+ *     The env's record is left as that many mgdp_envs_step calls would leave it, so a later call
+ *     continues where this one stopped.  Trace (both pointers or neither): for the first trace_len
+ *     steps the state index [trace_len][B] int32 and the env action [trace_len][B] int8, -1 where
+ *     no step was taken.
+ * *_device: device pointers, asynchronous on the handle's stream.  The others take host buffers
+ * (outputs may be NULL), copy pi to the device for the call and synchronise. */
+int mgdp_envs_policy_actions_device(mgdp_envs *envs, int32_t model, const int8_t *d_pi, int32_t T,
+                                    int32_t *d_actions, int32_t *d_status);
+int mgdp_envs_rollout_device(mgdp_envs *envs, int32_t model, const int8_t *d_pi, int32_t T, int32_t n_max,
+                             int32_t *d_steps, double *d_ret, uint8_t *d_terminated, uint8_t *d_truncated,
+                             int32_t *d_status, int32_t *d_trace_state, int8_t *d_trace_action, int32_t trace_len);
+int mgdp_envs_policy_actions(mgdp_envs *envs, int32_t model, const int8_t *pi, int32_t T, int32_t *actions,
+                             int32_t *status);
+int mgdp_envs_rollout(mgdp_envs *envs, int32_t model, const int8_t *pi, int32_t T, int32_t n_max, int32_t *steps,
+                      double *ret, uint8_t *terminated, uint8_t *truncated, int32_t *status, int32_t *trace_state,
+                      int8_t *trace_action, int32_t trace_len);
 /* HIP-event timing of the step kernel launches (begin/end timestamps of each dispatch, as the
- * rocprofv3 kernel trace reports them); kernel_time synchronises the stream and returns the total
- * since enable_timing. */
+ * rocprofv3 kernel trace reports them) and of the policy-lookup and rollout launches;
+ * kernel_time synchronises the stream and returns the total since enable_timing. */
 int mgdp_envs_enable_timing(mgdp_envs *envs, int32_t on);
 int mgdp_envs_kernel_time(mgdp_envs *envs, double *total_ms, int64_t *launches);
 /* Read back env state: enc B*W*H*3 (x-major), agent B*3, carry B*2 (type,color; 0 = none),

@@ -5,6 +5,8 @@ Hot path (HIP, gfx950, libmgdp.so behind include/mgdp.h):
   * Jacobi value iteration over (pos, dir[, has_key, door_open]) (csrc/vi.hip)
   * policy evaluation (V^pi of a given policy), greedy improvement and policy iteration on the
     same model and stopping rule                              (csrc/vi_eval.h)
+  * tabular policies executed on resident envs: policy lookup and the fused rollout, many steps
+    of every env in one launch                                (csrc/envs_rollout.h)
 Host side (this package): the reference's env API, registry and grid generators, the DP front end
 and the multi-GPU driver.  See DESIGN.md.
 """
@@ -14,6 +16,6 @@ from .minigrid_env import MiniGridEnv, MissionSpace
 from .envs import CrossingEnv, DistShiftEnv, DoorKeyEnv, EmptyEnv, FourRoomsEnv, LavaGapEnv
 from .registry import EnvSpec, make, register, registry
 from .dp import ValueIteration, VIResult, policy_evaluation, policy_iteration, value_iteration
-from .vector import MiniGridVecEnv
+from .vector import MiniGridVecEnv, RolloutResult
 
 __version__ = "0.1.0"

@@ -399,6 +399,8 @@ envs_step_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ age
     copy_out(obs + (long long)e0 * OB, smem, n * OB);
 }
 
+#include "envs_rollout.h"  // tabular policies on resident envs: policy lookup and the fused rollout
+
 }  // namespace mgdp
 
 using namespace mgdp;
@@ -419,6 +421,12 @@ struct mgdp_envs {
     size_t stage_bytes = 0;
     double death_cost = -1.0;
     int group = 2;  // lanes per env in envs_step_kernel (MGDP_STEP_GROUP = 1, 2, 4 or 8; 2 measured fastest)
+    // rollouts (envs_rollout.h): host-call scratch (the policy and the trace), grown on demand;
+    // roll_reader: -1 = LDS planes whenever 64 of them fit, 0 / 1 = MGDP_ROLLOUT_READER=hbm / lds
+    uint8_t *d_roll = nullptr;
+    size_t roll_bytes = 0;
+    int roll_reader = -1;
+    bool roll_pi_lds = false;  // MGDP_ROLLOUT_PI=lds: the A/B's other side
     // step-kernel timing (mgdp_envs_enable_timing): pooled event pairs handed to hipExtLaunchKernelGGL
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
@@ -442,17 +450,9 @@ int timed_collect(mgdp_envs *E) {  // after a stream sync
 
 EnvGeo env_geo(const mgdp_envs *E) { return EnvGeo{E->B, E->W, E->H, E->HWp, E->vs, E->nd_mask, E->death_cost}; }
 
-int launch_step(mgdp_envs *E, const int32_t *d_act, uint8_t *d_obs, int32_t *d_dir, double *d_rew,
-                uint8_t *d_term, uint8_t *d_trunc, int32_t *d_status, int observe_only) {
-    const int ne = kGroupBlock / E->group;
-    const int grid = (E->B + ne - 1) / ne;
-    const int smem = (int)round_up(ne * E->vs * E->vs * 3, 16) + ne * ((E->vs + 1) * kWinRow + 4);
-    auto pick = [&](auto k7, auto k5, auto k3) { return E->vs == 7 ? k7 : E->vs == 5 ? k5 : k3; };
-    auto k = E->group == 8   ? pick(envs_step_kernel<7, 8>, envs_step_kernel<5, 8>, envs_step_kernel<3, 8>)
-             : E->group == 4 ? pick(envs_step_kernel<7, 4>, envs_step_kernel<5, 4>, envs_step_kernel<3, 4>)
-             : E->group == 1 ? pick(envs_step_kernel<7, 1>, envs_step_kernel<5, 1>, envs_step_kernel<3, 1>)
-                             : pick(envs_step_kernel<7, 2>, envs_step_kernel<5, 2>, envs_step_kernel<3, 2>);
-    hipEvent_t ta = nullptr, tb = nullptr;
+// The event pair of the next timed launch (null, null with timing off).
+int timing_pair(mgdp_envs *E, hipEvent_t &ta, hipEvent_t &tb) {
+    ta = tb = nullptr;
     if (E->timing) {
         if (E->ev.size() >= 4096) {  // bound the pending pairs
             MGDP_HIP(hipStreamSynchronize(E->stream));
@@ -470,10 +470,85 @@ int launch_step(mgdp_envs *E, const int32_t *d_act, uint8_t *d_obs, int32_t *d_d
         ta = p.first;
         tb = p.second;
     }
+    return 0;
+}
+
+int launch_step(mgdp_envs *E, const int32_t *d_act, uint8_t *d_obs, int32_t *d_dir, double *d_rew,
+                uint8_t *d_term, uint8_t *d_trunc, int32_t *d_status, int observe_only) {
+    const int ne = kGroupBlock / E->group;
+    const int grid = (E->B + ne - 1) / ne;
+    const int smem = (int)round_up(ne * E->vs * E->vs * 3, 16) + ne * ((E->vs + 1) * kWinRow + 4);
+    auto pick = [&](auto k7, auto k5, auto k3) { return E->vs == 7 ? k7 : E->vs == 5 ? k5 : k3; };
+    auto k = E->group == 8   ? pick(envs_step_kernel<7, 8>, envs_step_kernel<5, 8>, envs_step_kernel<3, 8>)
+             : E->group == 4 ? pick(envs_step_kernel<7, 4>, envs_step_kernel<5, 4>, envs_step_kernel<3, 4>)
+             : E->group == 1 ? pick(envs_step_kernel<7, 1>, envs_step_kernel<5, 1>, envs_step_kernel<3, 1>)
+                             : pick(envs_step_kernel<7, 2>, envs_step_kernel<5, 2>, envs_step_kernel<3, 2>);
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
     hipExtLaunchKernelGGL(k, dim3(grid), dim3(kGroupBlock), smem, E->stream, ta, tb, 0, env_geo(E), E->d_cell, E->d_agent,
                        E->d_carry, E->d_cont, E->d_ccont, E->d_max, E->d_see, d_act, d_obs, d_dir, d_rew, d_term, d_trunc, d_status,
                        observe_only);
     MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- tabular policies on resident envs (envs_rollout.h) --------------------
+constexpr int kRollLdsMax = 160 * 1024 - 2048;  // the 64 padded planes; the rest is the staging pass's words
+
+int roll_check(const mgdp_envs *E, int32_t model, const void *pi, int32_t T, int *S) {
+    MGDP_CHECK(E && pi, MGDP_E_INVALID, "null argument");
+    MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
+    MGDP_CHECK(T >= 1, MGDP_E_INVALID, "T must be >= 1 (1 = a stationary policy), got %d", T);
+    MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
+    *S = E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16);
+    return 0;
+}
+
+int launch_policy_actions(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32_t T, int S, int32_t *d_actions,
+                          int32_t *d_status) {
+    auto k = model == MGDP_MODEL_XYD ? envs_policy_actions_kernel<kRollXYD> : envs_policy_actions_kernel<kRollDoorKey>;
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(k, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, ta, tb, 0, env_geo(E), E->d_cell, E->d_agent,
+                          E->d_carry, d_pi, T, S, d_actions, d_status);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
+    const int lds_bytes = kRollWave * roll_stride(E->HWp);
+    const bool fits = lds_bytes <= kRollLdsMax;
+    const bool lds = E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits);
+    // MGDP_ROLLOUT_PI=lds: a stationary policy's rows staged too, where they fit beside the planes
+    const int pi_lds_bytes = roll_pi_base(E->HWp) + kRollWave * roll_pi_stride(r.S);
+    const bool pil = E->roll_pi_lds && lds && r.T == 1 && pi_lds_bytes <= kRollLdsMax && ((uintptr_t)r.pi & 3) == 0;
+    auto k = model == MGDP_MODEL_XYD
+                 ? (pil ? envs_rollout_kernel<kRollXYD, true, true> : lds ? envs_rollout_kernel<kRollXYD, true> : envs_rollout_kernel<kRollXYD, false>)
+                 : (pil   ? envs_rollout_kernel<kRollDoorKey, true, true>
+                    : lds ? envs_rollout_kernel<kRollDoorKey, true>
+                          : envs_rollout_kernel<kRollDoorKey, false>);
+    const int smem = pil ? pi_lds_bytes : lds ? lds_bytes : 0;
+    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    if (r.trace_len > 0) {  // unused entries are -1
+        MGDP_HIP(hipMemsetAsync(r.tr_state, 0xff, sizeof(int32_t) * (size_t)r.trace_len * E->B, E->stream));
+        MGDP_HIP(hipMemsetAsync(r.tr_act, 0xff, (size_t)r.trace_len * E->B, E->stream));
+    }
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
+                          E->d_cell, E->d_agent, E->d_carry, E->d_max, r);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+int roll_scratch(mgdp_envs *E, size_t need) {
+    if (E->roll_bytes >= need) return 0;
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    if (E->d_roll) MGDP_HIP(hipFree(E->d_roll));
+    E->d_roll = nullptr;
+    E->roll_bytes = 0;
+    MGDP_HIP(hipMalloc((void **)&E->d_roll, need));
+    E->roll_bytes = need;
     return 0;
 }
 
@@ -495,9 +570,21 @@ int mgdp_envs_create(int32_t device, int32_t B, int32_t W, int32_t H, int32_t vi
         MGDP_CHECK(group == 1 || group == 2 || group == 4 || group == 8, MGDP_E_INVALID,
                    "MGDP_STEP_GROUP must be 1, 2, 4 or 8 (got %s)", ev);
     }
+    int roll_reader = -1;
+    if (const char *ev = std::getenv("MGDP_ROLLOUT_READER")) {  // A/B of the rollout's cell reader (tools/probe_rollout.py)
+        roll_reader = !std::strcmp(ev, "hbm") ? 0 : !std::strcmp(ev, "lds") ? 1 : -2;
+        MGDP_CHECK(roll_reader != -2, MGDP_E_INVALID, "MGDP_ROLLOUT_READER must be hbm or lds (got %s)", ev);
+    }
+    bool roll_pi_lds = false;
+    if (const char *ev = std::getenv("MGDP_ROLLOUT_PI")) {
+        MGDP_CHECK(!std::strcmp(ev, "lds") || !std::strcmp(ev, "hbm"), MGDP_E_INVALID, "MGDP_ROLLOUT_PI must be hbm or lds (got %s)", ev);
+        roll_pi_lds = !std::strcmp(ev, "lds");
+    }
     DeviceGuard guard(device);
     mgdp_envs *E = new mgdp_envs();
     E->group = group;
+    E->roll_reader = roll_reader;
+    E->roll_pi_lds = roll_pi_lds;
     E->device = device; E->B = B; E->W = W; E->H = H; E->HW = W * H; E->HWp = (int)round_up(W * H, 16);
     E->vs = view_size;
     const size_t P = (size_t)B * E->HWp;
@@ -531,7 +618,8 @@ int mgdp_envs_destroy(mgdp_envs *E) {
     DeviceGuard guard(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     void *ps[] = {E->d_cell, E->d_see, E->d_agent, E->d_carry, E->d_max, E->d_act,
-                  E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage};
+                  E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage,
+                  E->d_roll};
     for (void *p : ps) (void)hipFree(p);
     for (auto &p : E->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &p : E->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -876,6 +964,77 @@ int mgdp_envs_get_contents(mgdp_envs *E, uint8_t *contents, int32_t *carry_conte
             carry_contents[3 * b] = t; carry_contents[3 * b + 1] = c; carry_contents[3 * b + 2] = s;
         }
     }
+    return 0;
+}
+
+// ---- policy lookup and fused rollout ---------------------------------------
+int mgdp_envs_policy_actions_device(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32_t T, int32_t *d_actions,
+                                    int32_t *d_status) {
+    int S = 0;
+    if (int rc = roll_check(E, model, d_pi, T, &S)) return rc;
+    MGDP_CHECK(d_actions && d_status, MGDP_E_INVALID, "null argument");
+    DeviceGuard guard(E->device);
+    return launch_policy_actions(E, model, d_pi, T, S, d_actions, d_status);
+}
+
+int mgdp_envs_rollout_device(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32_t T, int32_t n_max, int32_t *d_steps,
+                             double *d_ret, uint8_t *d_terminated, uint8_t *d_truncated, int32_t *d_status,
+                             int32_t *d_trace_state, int8_t *d_trace_action, int32_t trace_len) {
+    int S = 0;
+    if (int rc = roll_check(E, model, d_pi, T, &S)) return rc;
+    MGDP_CHECK(d_steps && d_ret && d_terminated && d_truncated && d_status, MGDP_E_INVALID, "null argument");
+    MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
+    const bool trace = d_trace_state && d_trace_action;
+    MGDP_CHECK(trace || (!d_trace_state && !d_trace_action), MGDP_E_INVALID, "a trace needs both of its buffers");
+    DeviceGuard guard(E->device);
+    const RolloutArgs r{d_pi, T, S, n_max, trace ? trace_len : 0, d_steps, d_ret, d_terminated, d_truncated, d_status,
+                        trace ? d_trace_state : nullptr, trace ? d_trace_action : nullptr};
+    return launch_rollout(E, model, r);
+}
+
+int mgdp_envs_policy_actions(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, int32_t *actions, int32_t *status) {
+    int S = 0;
+    if (int rc = roll_check(E, model, pi, T, &S)) return rc;
+    MGDP_CHECK(actions, MGDP_E_INVALID, "null argument");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B, n_pi = (size_t)T * B * S;
+    if (int rc = roll_scratch(E, n_pi)) return rc;
+    MGDP_HIP(hipMemcpyAsync(E->d_roll, pi, n_pi, hipMemcpyHostToDevice, E->stream));
+    if (int rc = launch_policy_actions(E, model, (const int8_t *)E->d_roll, T, S, E->d_act, E->d_status)) return rc;
+    MGDP_HIP(hipMemcpyAsync(actions, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int mgdp_envs_rollout(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, int32_t n_max, int32_t *steps, double *ret,
+                      uint8_t *terminated, uint8_t *truncated, int32_t *status, int32_t *trace_state,
+                      int8_t *trace_action, int32_t trace_len) {
+    int S = 0;
+    if (int rc = roll_check(E, model, pi, T, &S)) return rc;
+    MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
+    const bool trace = trace_state && trace_action && trace_len > 0;
+    MGDP_CHECK(trace || (!trace_state && !trace_action) || trace_len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B, n_pi = round_up((size_t)T * B * S, 16), n_tr = trace ? (size_t)trace_len * B : 0;
+    if (int rc = roll_scratch(E, n_pi + 5 * n_tr)) return rc;
+    int32_t *d_ts = reinterpret_cast<int32_t *>(E->d_roll + n_pi);
+    int8_t *d_ta = reinterpret_cast<int8_t *>(E->d_roll + n_pi + 4 * n_tr);
+    MGDP_HIP(hipMemcpyAsync(E->d_roll, pi, (size_t)T * B * S, hipMemcpyHostToDevice, E->stream));
+    // the step entry points' per-env buffers serve as outputs: d_act holds the step counts
+    const RolloutArgs r{(const int8_t *)E->d_roll, T, S, n_max, trace ? trace_len : 0, E->d_act, E->d_rew, E->d_term,
+                        E->d_trunc, E->d_status, trace ? d_ts : nullptr, trace ? d_ta : nullptr};
+    if (int rc = launch_rollout(E, model, r)) return rc;
+    if (steps) MGDP_HIP(hipMemcpyAsync(steps, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (ret) MGDP_HIP(hipMemcpyAsync(ret, E->d_rew, 8 * B, hipMemcpyDeviceToHost, E->stream));
+    if (terminated) MGDP_HIP(hipMemcpyAsync(terminated, E->d_term, B, hipMemcpyDeviceToHost, E->stream));
+    if (truncated) MGDP_HIP(hipMemcpyAsync(truncated, E->d_trunc, B, hipMemcpyDeviceToHost, E->stream));
+    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (trace) {
+        MGDP_HIP(hipMemcpyAsync(trace_state, d_ts, 4 * n_tr, hipMemcpyDeviceToHost, E->stream));
+        MGDP_HIP(hipMemcpyAsync(trace_action, d_ta, n_tr, hipMemcpyDeviceToHost, E->stream));
+    }
+    MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }
 

@@ -561,6 +561,16 @@ class ValueIteration:
         return VIResult(self.values(), self.policy(), self.sweeps, self.converged, self.dv, self.model,
                         self.W, self.H)
 
+    def device_buffers(self) -> tuple[int, int]:
+        """(V_ptr, pi_ptr): device pointers of the handle's V (B*S of its dtype) and pi (B*S int8) buffers
+        (mgdp_vi_device_buffers), for zero-copy consumers such as MiniGridVecEnv.rollout_device.  The
+        handle is synchronised first, so a resident lone-grid server's result is in HBM; the pointers
+        stay valid until close() and are overwritten by the next solve / evaluate / improve."""
+        self.synchronize()
+        dV, dpi = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(self.L.mgdp_vi_device_buffers(self.h, ctypes.byref(dV), ctypes.byref(dpi)), "mgdp_vi_device_buffers")
+        return int(dV.value or 0), int(dpi.value or 0)
+
     def synchronize(self):
         """Complete all work of the handle (a resident lone-grid server leaves, the stream drains)."""
         _lib.check(self.L.mgdp_vi_synchronize(self.h), "mgdp_vi_synchronize")

@@ -8,11 +8,28 @@ Grids are generated on the host by the reference-exact generators (envs.py) and 
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib, gen
 from .registry import make
+
+
+@dataclass
+class RolloutResult:
+    """What MiniGridVecEnv.rollout collected, per env."""
+    steps: np.ndarray       # (B,) int32 steps taken in this call
+    ret: np.ndarray         # (B,) float64 their rewards, summed in step order (the env's own _reward / NoDeath cost)
+    terminated: np.ndarray  # (B,) bool flags of the last step taken
+    truncated: np.ndarray   # (B,) bool
+    status: np.ndarray      # (B,) int32: 0, or the MGDP_E_* code that stopped the env (it was not stepped further)
+    states: np.ndarray | None = None   # trace: (max steps, B) int32 state index before each step, -1 unused
+    actions: np.ndarray | None = None  # trace: (max steps, B) int8 env action of each step, -1 unused
+
+    @property
+    def ok(self) -> bool:
+        return bool((self.status == 0).all())
 
 
 class MiniGridVecEnv:
@@ -63,6 +80,7 @@ class MiniGridVecEnv:
         self._seeds = np.zeros(B, np.int64)
         self._next_seed = 0
         self._held = False  # Box contents planes in use (set_contents)
+        self._ms_cap = self.max_steps  # the largest max_steps loaded: bounds a rollout's trace
 
     def close(self):
         if getattr(self, "h", None):
@@ -89,6 +107,7 @@ class MiniGridVecEnv:
         see = np.full(B, 1 if self.see_through else 0, np.uint8)
         if see_through is not None:
             see[:] = np.asarray(see_through, np.uint8)
+        self._ms_cap = max(int(ms.max()), self._ms_cap if mask is not None else 0)
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         _lib.check(self.L.mgdp_envs_load(self.h, _lib.ptr(enc), _lib.ptr(agent), _lib.ptr(ms), _lib.ptr(see),
                                          _lib.ptr(m)), "mgdp_envs_load")
@@ -189,6 +208,111 @@ class MiniGridVecEnv:
                                           p(truncated), p(status))
         if rc:
             _lib.check(rc, "mgdp_envs_step_device")
+
+    # ---------------------------------------------------------------- tabular policies
+    def _policy_args(self, policy, model):
+        """(pi int8 (T*B, S) contiguous, T, model id) of a (B, S) / (T, B, S) integer array or a VIResult,
+        checked before any device work (as ValueIteration._check_policy)."""
+        from . import dp
+        from .envs import DoorKeyEnv
+
+        if self.autoreset:
+            raise ValueError("rollout / policy_actions run the envs as they are: not with autoreset=True")
+        if self._held:
+            raise ValueError("Box contents (set_contents) are in use: outside the XYD and DoorKey models")
+        if isinstance(policy, dp.VIResult):
+            if model == "auto":
+                model = policy.model
+            policy = policy.pi
+        if model == "auto":
+            model = "doorkey" if isinstance(self._gen, DoorKeyEnv) else "xyd"
+        if model not in dp.MODELS:
+            raise ValueError(f"unknown model {model!r}")
+        a = np.asarray(policy)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
+        B, S = self.num_envs, dp.n_states(model, self.W, self.H)
+        if a.shape != (B, S) and (a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (B, S)):
+            raise ValueError(f"policy of shape {a.shape} is neither {(B, S)} nor (T, {B}, {S}) of the {model} model")
+        if a.dtype != np.int8:
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError("policy entries do not fit int8 action lanes")
+            a = a.astype(np.int8)
+        T = 1 if a.ndim == 2 else a.shape[0]
+        if a.ndim == 3 and T == 1:
+            raise ValueError("a time-indexed policy needs T > 1 rows; pass (B, S) for a stationary one")
+        return np.ascontiguousarray(a), T, dp.MODELS[model]
+
+    def policy_actions(self, policy, model: str = "auto", return_status: bool = False):
+        """(B,) int32: the env action `policy` takes at every env's current state (mgdp_envs_policy_actions),
+        -1 where it has none (a lane outside the model's, a grid or carry outside the model, step_count
+        beyond a time-indexed policy); return_status also gives the per-env status."""
+        pi, T, mid = self._policy_args(policy, model)
+        acts = np.zeros(self.num_envs, np.int32)
+        status = np.zeros(self.num_envs, np.int32)
+        _lib.check(self.L.mgdp_envs_policy_actions(self.h, mid, _lib.ptr(pi), T, _lib.ptr(acts), _lib.ptr(status)),
+                   "mgdp_envs_policy_actions")
+        return (acts, status) if return_status else acts
+
+    def rollout(self, policy, model: str = "auto", max_steps: int | None = None,
+                trace: bool | int = False) -> "RolloutResult":
+        """Execute a tabular policy on every env from its current state, in one launch
+        (mgdp_envs_rollout): until the env terminates, truncates or has taken max_steps steps (None:
+        no budget).  policy: (B, S) int8 action lanes in ValueIteration.policy()'s order, (T, B, S) as
+        policy_t() (the row is step_count), or a VIResult.  A per-env problem never raises: it is that
+        env's status (see RolloutResult).  trace=True records states and actions of every step taken (up
+        to the envs' max_steps rows of B entries each are allocated), trace=n those of the first n steps.
+        A later call continues where this one stopped."""
+        pi, T, mid = self._policy_args(policy, model)
+        B = self.num_envs
+        n_max = 0 if max_steps is None else int(max_steps)
+        if max_steps is not None and n_max <= 0:
+            raise ValueError("max_steps must be > 0 (None: no budget)")
+        steps, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        ret = np.zeros(B, np.float64)
+        term, trunc = np.zeros(B, np.uint8), np.zeros(B, np.uint8)
+        tlen = 0
+        ts = ta = None
+        if trace:  # no env outlives its max_steps from step_count 0; a budget bounds it further
+            tlen = max(int(self._ms_cap), 1) if trace is True else int(trace)
+            if tlen <= 0:
+                raise ValueError("trace must be True, False or a positive number of steps")
+            tlen = min(tlen, n_max) if n_max else tlen
+            ts, ta = np.empty((tlen, B), np.int32), np.empty((tlen, B), np.int8)
+        _lib.check(self.L.mgdp_envs_rollout(self.h, mid, _lib.ptr(pi), T, n_max, _lib.ptr(steps), _lib.ptr(ret),
+                                            _lib.ptr(term), _lib.ptr(trunc), _lib.ptr(status), _lib.ptr(ts), _lib.ptr(ta),
+                                            tlen), "mgdp_envs_rollout")
+        if trace:
+            k = min(int(steps.max(initial=0)), tlen)
+            ts, ta = ts[:k].copy(), ta[:k].copy()
+        return RolloutResult(steps, ret, term.astype(bool), trunc.astype(bool), status, ts, ta)
+
+    def policy_actions_device(self, pi, T: int, model: str, actions, status):
+        """policy_actions on device buffers (torch CUDA tensors or raw pointers), asynchronous on the
+        handle's stream: pi int8 [T][B][S] (T = 1: [B][S]), actions / status int32 (B,)."""
+        from . import dp
+
+        p = _lib.ptr
+        rc = self.L.mgdp_envs_policy_actions_device(self.h, dp.MODELS[model], p(pi), int(T), p(actions), p(status))
+        if rc:
+            _lib.check(rc, "mgdp_envs_policy_actions_device")
+
+    def rollout_device(self, pi, T: int, model: str, max_steps, steps, ret, terminated, truncated, status,
+                       trace_state=None, trace_action=None, trace_len: int = 0):
+        """rollout on device buffers (torch CUDA tensors or raw pointers), asynchronous on the handle's
+        stream: pi int8 [T][B][S], e.g. ValueIteration.device_buffers()[1] of a solved handle (no host
+        copy); steps / status int32, ret float64, terminated / truncated uint8, all (B,); the trace
+        int32 / int8 [trace_len][B] or None.  max_steps None or <= 0: no budget."""
+        from . import dp
+
+        if self.autoreset:
+            raise ValueError("rollout runs the envs as they are: not with autoreset=True")
+        p = _lib.ptr
+        rc = self.L.mgdp_envs_rollout_device(self.h, dp.MODELS[model], p(pi), int(T), int(max_steps or 0), p(steps), p(ret),
+                                             p(terminated), p(truncated), p(status), p(trace_state), p(trace_action),
+                                             int(trace_len))
+        if rc:
+            _lib.check(rc, "mgdp_envs_rollout_device")
 
     def enable_timing(self, on: bool):
         """Time every step-kernel launch with a HIP event pair on the launch itself."""
