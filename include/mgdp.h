@@ -380,8 +380,35 @@ int mgdp_envs_policy_actions(mgdp_envs *envs, int32_t model, const int8_t *pi, i
 int mgdp_envs_rollout(mgdp_envs *envs, int32_t model, const int8_t *pi, int32_t T, int32_t n_max, int32_t *steps,
                       double *ret, uint8_t *terminated, uint8_t *truncated, int32_t *status, int32_t *trace_state,
                       int8_t *trace_action, int32_t trace_len);
+/* Slip: the reference's StochasticActionWrapper (wrappers.py:775-796) on the resident envs, with one
+ * PCG64 stream per env (additive entry points, the ABI version is unchanged).
+ * Env b's stream is numpy.random.Generator(PCG64(SeedSequence(seed0 + b))) (seed0 + b mod 2^64); its
+ * record -- the 128-bit state and increment and PCG64's buffered half-word -- lives on the handle and
+ * persists across calls.  One slip decision on an env action a: u = random() (one 64-bit draw);
+ * u < prob keeps a, else a becomes random_action, or integers(0, 6) (numpy's buffered 32-bit Lemire
+ * draw) where random_action is -1.
+ *   mgdp_envs_set_slip: enqueued on the handle's stream.  prob and random_action hold for the whole
+ *     handle; the masked streams (NULL: all) are (re)seeded from seed0 + b.  MGDP_E_INVALID for prob
+ *     outside [0, 1] or NaN, random_action outside -1..6, and a mask on the first call (or the first
+ *     after clear_slip), which must seed every stream.  load / reset / set_state leave the streams alone.
+ *   mgdp_envs_clear_slip: the handle behaves as if slip had never been set.
+ *   With slip set, mgdp_envs_rollout* take one slip decision per step between the policy lookup and
+ *     the step: a failed lookup (MGDP_E_INVALID, MGDP_E_ACTION) draws nothing, a draw is never rolled
+ *     back (MGDP_E_BOUNDS leaves the env as it was and the stream advanced), NoDeath and the trace see
+ *     the executed action, and the model check stays at entry only.  mgdp_envs_step*,
+ *     mgdp_envs_policy_actions* never draw.
+ *   mgdp_envs_slip_actions*: one slip decision per env on in[b], written to out[b] (in == out is
+ *     allowed); a negative in[b] (policy_actions' "none") passes through and draws nothing.
+ *   mgdp_envs_get_slip_streams: state B*4 = (state hi, state lo, inc hi, inc lo) and half B*2 =
+ *     (has_uint32, uinteger) per env, numpy's bit_generator.state integers; either may be NULL.
+ * slip_actions and get_slip_streams return MGDP_E_INVALID on a handle without slip. */
+int mgdp_envs_set_slip(mgdp_envs *envs, double prob, int32_t random_action, uint64_t seed0, const uint8_t *mask);
+int mgdp_envs_clear_slip(mgdp_envs *envs);
+int mgdp_envs_get_slip_streams(mgdp_envs *envs, uint64_t *state, uint32_t *half);
+int mgdp_envs_slip_actions_device(mgdp_envs *envs, const int32_t *d_in, int32_t *d_out);
+int mgdp_envs_slip_actions(mgdp_envs *envs, const int32_t *in, int32_t *out);
 /* HIP-event timing of the step kernel launches (begin/end timestamps of each dispatch, as the
- * rocprofv3 kernel trace reports them) and of the policy-lookup and rollout launches;
+ * rocprofv3 kernel trace reports them) and of the policy-lookup, slip-action and rollout launches;
  * kernel_time synchronises the stream and returns the total since enable_timing. */
 int mgdp_envs_enable_timing(mgdp_envs *envs, int32_t on);
 int mgdp_envs_kernel_time(mgdp_envs *envs, double *total_ms, int64_t *launches);

@@ -132,6 +132,11 @@ SIGNATURES = {
     "mgdp_envs_rollout_device": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "mgdp_envs_policy_actions": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P]),
     "mgdp_envs_rollout": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "mgdp_envs_set_slip": (ctypes.c_int, [_P, ctypes.c_double, _I32, ctypes.c_uint64, _P]),
+    "mgdp_envs_clear_slip": (ctypes.c_int, [_P]),
+    "mgdp_envs_get_slip_streams": (ctypes.c_int, [_P, _P, _P]),
+    "mgdp_envs_slip_actions_device": (ctypes.c_int, [_P, _P, _P]),
+    "mgdp_envs_slip_actions": (ctypes.c_int, [_P, _P, _P]),
     "mgdp_envs_enable_timing": (ctypes.c_int, [_P, _I32]),
     "mgdp_envs_kernel_time": (ctypes.c_int, [_P, _DP, _I64P]),
     "mgdp_envs_get_state": (ctypes.c_int, [_P, _P, _P, _P, _P]),

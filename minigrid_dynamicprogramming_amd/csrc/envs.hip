@@ -26,6 +26,7 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "pcg64.h"
 
 namespace mgdp {
 
@@ -427,6 +428,13 @@ struct mgdp_envs {
     size_t roll_bytes = 0;
     int roll_reader = -1;
     bool roll_pi_lds = false;  // MGDP_ROLLOUT_PI=lds: the A/B's other side
+    // slip: per-env PCG64 records, allocated by the first mgdp_envs_set_slip
+    bool slip = false;
+    double slip_p = 1.0;
+    int slip_ra = -1;
+    uint64_t *d_slip_state = nullptr;  // [B][4] state hi, lo, inc hi, lo
+    uint32_t *d_slip_half = nullptr;   // [B][2] has_uint32, uinteger
+    uint8_t *d_slip_mask = nullptr;    // [B] a masked reseed's mask
     // step-kernel timing (mgdp_envs_enable_timing): pooled event pairs handed to hipExtLaunchKernelGGL
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
@@ -515,6 +523,19 @@ int launch_policy_actions(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32
     return 0;
 }
 
+SlipArgs slip_args(const mgdp_envs *E) { return SlipArgs{E->slip_p, E->slip_ra, E->d_slip_state, E->d_slip_half}; }
+
+using RolloutKernel = void (*)(EnvGeo, uint8_t *, int32_t *, int32_t *, const int32_t *, RolloutArgs, SlipArgs);
+template <bool SLIP>
+RolloutKernel rollout_kernel(int32_t model, bool lds, bool pil) {
+    return model == MGDP_MODEL_XYD ? (pil   ? envs_rollout_kernel<kRollXYD, true, true, SLIP>
+                                      : lds ? envs_rollout_kernel<kRollXYD, true, false, SLIP>
+                                            : envs_rollout_kernel<kRollXYD, false, false, SLIP>)
+                                   : (pil   ? envs_rollout_kernel<kRollDoorKey, true, true, SLIP>
+                                      : lds ? envs_rollout_kernel<kRollDoorKey, true, false, SLIP>
+                                            : envs_rollout_kernel<kRollDoorKey, false, false, SLIP>);
+}
+
 int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
     const int lds_bytes = kRollWave * roll_stride(E->HWp);
     const bool fits = lds_bytes <= kRollLdsMax;
@@ -522,11 +543,7 @@ int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
     // MGDP_ROLLOUT_PI=lds: a stationary policy's rows staged too, where they fit beside the planes
     const int pi_lds_bytes = roll_pi_base(E->HWp) + kRollWave * roll_pi_stride(r.S);
     const bool pil = E->roll_pi_lds && lds && r.T == 1 && pi_lds_bytes <= kRollLdsMax && ((uintptr_t)r.pi & 3) == 0;
-    auto k = model == MGDP_MODEL_XYD
-                 ? (pil ? envs_rollout_kernel<kRollXYD, true, true> : lds ? envs_rollout_kernel<kRollXYD, true> : envs_rollout_kernel<kRollXYD, false>)
-                 : (pil   ? envs_rollout_kernel<kRollDoorKey, true, true>
-                    : lds ? envs_rollout_kernel<kRollDoorKey, true>
-                          : envs_rollout_kernel<kRollDoorKey, false>);
+    const RolloutKernel k = E->slip ? rollout_kernel<true>(model, lds, pil) : rollout_kernel<false>(model, lds, pil);
     const int smem = pil ? pi_lds_bytes : lds ? lds_bytes : 0;
     if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     if (r.trace_len > 0) {  // unused entries are -1
@@ -536,7 +553,16 @@ int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
     hipEvent_t ta = nullptr, tb = nullptr;
     if (int rc = timing_pair(E, ta, tb)) return rc;
     hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
-                          E->d_cell, E->d_agent, E->d_carry, E->d_max, r);
+                          E->d_cell, E->d_agent, E->d_carry, E->d_max, r, slip_args(E));
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_slip_actions(mgdp_envs *E, const int32_t *d_in, int32_t *d_out) {
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(envs_slip_actions_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, ta, tb, 0, E->B,
+                          slip_args(E), d_in, d_out);
     MGDP_HIP(hipGetLastError());
     return 0;
 }
@@ -619,7 +645,7 @@ int mgdp_envs_destroy(mgdp_envs *E) {
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     void *ps[] = {E->d_cell, E->d_see, E->d_agent, E->d_carry, E->d_max, E->d_act,
                   E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage,
-                  E->d_roll};
+                  E->d_roll, E->d_slip_state, E->d_slip_half, E->d_slip_mask};
     for (void *p : ps) (void)hipFree(p);
     for (auto &p : E->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &p : E->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -1034,6 +1060,65 @@ int mgdp_envs_rollout(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, 
         MGDP_HIP(hipMemcpyAsync(trace_state, d_ts, 4 * n_tr, hipMemcpyDeviceToHost, E->stream));
         MGDP_HIP(hipMemcpyAsync(trace_action, d_ta, n_tr, hipMemcpyDeviceToHost, E->stream));
     }
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+// ---- slip: per-env PCG64 action noise ---------------------------------------
+int mgdp_envs_set_slip(mgdp_envs *E, double prob, int32_t random_action, uint64_t seed0, const uint8_t *mask) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(prob >= 0.0 && prob <= 1.0, MGDP_E_INVALID, "slip prob must be in [0, 1], got %g", prob);  // NaN fails both
+    MGDP_CHECK(random_action >= -1 && random_action <= 6, MGDP_E_INVALID,
+               "random_action must be an env action 0..6 or -1 (draw one of 0..5), got %d", random_action);
+    MGDP_CHECK(E->slip || !mask, MGDP_E_INVALID, "the first mgdp_envs_set_slip seeds every stream: no mask");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (!E->d_slip_state) MGDP_HIP(hipMalloc((void **)&E->d_slip_state, sizeof(uint64_t) * 4 * B));
+    if (!E->d_slip_half) MGDP_HIP(hipMalloc((void **)&E->d_slip_half, sizeof(uint32_t) * 2 * B));
+    if (!E->d_slip_mask) MGDP_HIP(hipMalloc((void **)&E->d_slip_mask, B));
+    if (mask) MGDP_HIP(hipMemcpyAsync(E->d_slip_mask, mask, B, hipMemcpyHostToDevice, E->stream));
+    E->slip_p = prob;
+    E->slip_ra = random_action;
+    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
+                       mask ? E->d_slip_mask : nullptr, slip_args(E));
+    MGDP_HIP(hipGetLastError());
+    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
+    E->slip = true;
+    return 0;
+}
+
+int mgdp_envs_clear_slip(mgdp_envs *E) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    E->slip = false;  // the records stay allocated; the next set_slip is a first call again
+    return 0;
+}
+
+int mgdp_envs_get_slip_streams(mgdp_envs *E, uint64_t *state, uint32_t *half) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (state) MGDP_HIP(hipMemcpyAsync(state, E->d_slip_state, sizeof(uint64_t) * 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (half) MGDP_HIP(hipMemcpyAsync(half, E->d_slip_half, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, E->stream));
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int mgdp_envs_slip_actions_device(mgdp_envs *E, const int32_t *d_in, int32_t *d_out) {
+    MGDP_CHECK(E && d_in && d_out, MGDP_E_INVALID, "null argument");
+    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    DeviceGuard guard(E->device);
+    return launch_slip_actions(E, d_in, d_out);
+}
+
+int mgdp_envs_slip_actions(mgdp_envs *E, const int32_t *in, int32_t *out) {
+    MGDP_CHECK(E && in && out, MGDP_E_INVALID, "null argument");
+    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    MGDP_HIP(hipMemcpyAsync(E->d_act, in, 4 * B, hipMemcpyHostToDevice, E->stream));
+    if (int rc = launch_slip_actions(E, E->d_act, E->d_act)) return rc;
+    MGDP_HIP(hipMemcpyAsync(out, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }

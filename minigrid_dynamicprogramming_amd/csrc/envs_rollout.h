@@ -4,12 +4,17 @@
 //   envs_policy_actions_kernel<MODEL>   one lane per env: the state index of the live env in the order
 //       of mgdp_vi_get_policy, the policy's lane there, the env action (-1: none) and a status.  No
 //       stepping: its output is what mgdp_envs_step_device takes.
-//   envs_rollout_kernel<MODEL, LDS, PILDS>  one lane per env, one wave per workgroup: every env is carried
+//   envs_rollout_kernel<MODEL, LDS, PILDS, SLIP>  one lane per env, one wave per workgroup: every env is carried
 //       through step_core until it terminates, truncates, fails or the budget ends -- no observation,
 //       no launch per step, no host in the loop.  LDS: the wave's 64 cell planes are staged into LDS
 //       with 16-byte loads (the model check and the DoorKey door index come out of the same pass), the
 //       loop steps on LDS and the planes go back once at exit if any env mutated its grid.  Otherwise
 //       the reader is the env's own plane in HBM (grids whose 64 planes do not fit a CU's LDS).
+//       SLIP: every step's action first passes the env's own PCG64 stream -- kept
+//       with probability prob, else random_action or integers(0, 6) -- held in registers for the whole
+//       loop and written back at exit.
+//   envs_slip_seed_kernel / envs_slip_actions_kernel  one lane per env: the stream of seed0 + b, and one
+//       slip decision on a given action (for step_device loops that want observations).
 //
 // The LDS stride per env is HWp + 4 bytes: HWp is a multiple of 16, so the stride is an odd number of
 // dwords and lane l's byte at the same cell offset falls into bank (l * odd + c) mod 32 -- distinct
@@ -134,10 +139,62 @@ __host__ __device__ inline int roll_stride(int HWp) { return HWp + 4; }
 __host__ __device__ inline int roll_pi_stride(int S) { return ((S >> 2) & 1) ? S : S + 4; }
 __host__ __device__ inline int roll_pi_base(int HWp) { return (kRollWave * roll_stride(HWp) + 15) & ~15; }
 
-template <int MODEL, bool LDS, bool PILDS = false>
+// ---- slip streams -----------------------------------------------------------
+// Env b's record: state[4 b ..] = (state hi, state lo, inc hi, inc lo), half[2 b ..] = (has_uint32, uinteger).
+struct SlipArgs {
+    double prob;
+    int random_action;  // -1: integers(0, 6)
+    uint64_t *state;
+    uint32_t *half;
+};
+
+__device__ __forceinline__ Pcg64 slip_load(const SlipArgs &sl, int e) {
+    const ulonglong2 st = reinterpret_cast<const ulonglong2 *>(sl.state)[2 * (long long)e];
+    const ulonglong2 in = reinterpret_cast<const ulonglong2 *>(sl.state)[2 * (long long)e + 1];
+    const uint2 h = reinterpret_cast<const uint2 *>(sl.half)[e];
+    return Pcg64(U128{st.x, st.y}, U128{in.x, in.y}, h.x != 0, h.y);
+}
+// The increment never changes: the state and the half-word go back.  numpy keeps the last buffered
+// half in uinteger after it is consumed, and so does buf.
+__device__ __forceinline__ void slip_store(const SlipArgs &sl, int e, const Pcg64 &r) {
+    reinterpret_cast<ulonglong2 *>(sl.state)[2 * (long long)e] = make_ulonglong2(r.state.hi, r.state.lo);
+    reinterpret_cast<uint2 *>(sl.half)[e] = make_uint2(r.has32 ? 1u : 0u, r.buf);
+}
+// One slip decision: u = random(); u < prob keeps the action, else random_action or integers(0, 6).
+__device__ __forceinline__ int slip_decide(Pcg64 &r, double prob, int random_action, int a) {
+    const double u = r.next_double();
+    if (u < prob) return a;
+    return random_action >= 0 ? random_action : r.integers(0, 6);
+}
+
+__global__ void __launch_bounds__(256)
+envs_slip_seed_kernel(int B, uint64_t seed0, const uint8_t *__restrict__ mask, SlipArgs sl) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B || (mask && !mask[e])) return;
+    const Pcg64 r(seed0 + (uint64_t)e);
+    reinterpret_cast<ulonglong2 *>(sl.state)[2 * (long long)e + 1] = make_ulonglong2(r.inc.hi, r.inc.lo);
+    slip_store(sl, e, r);
+}
+
+// in == out is allowed (each lane reads its entry before it writes it).  A negative action is
+// policy_actions' "none": it passes through and draws nothing, as a failed lookup does in the rollout.
+__global__ void __launch_bounds__(256)
+envs_slip_actions_kernel(int B, SlipArgs sl, const int32_t *in, int32_t *out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B) return;
+    int a = in[e];
+    if (a >= 0) {
+        Pcg64 r = slip_load(sl, e);
+        a = slip_decide(r, sl.prob, sl.random_action, a);
+        slip_store(sl, e, r);
+    }
+    out[e] = a;
+}
+
+template <int MODEL, bool LDS, bool PILDS = false, bool SLIP = false>
 __global__ void __launch_bounds__(kRollWave)
 envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ agent, int32_t *__restrict__ carry,
-                    const int32_t *__restrict__ max_steps, RolloutArgs r) {
+                    const int32_t *__restrict__ max_steps, RolloutArgs r, SlipArgs sl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_bad[kRollWave], s_ndoor[kRollWave], s_door[kRollWave], s_doorcode[kRollWave], s_nkey[kRollWave],
         s_keyc[kRollWave];
@@ -198,6 +255,8 @@ envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ 
     int n = 0, term = 0, trunc = 0, dirty = 0;
     double ret = 0.0;
     bool live = mine && status == MGDP_OK;
+    Pcg64 rng(U128{0, 0}, U128{0, 0}, false, 0u);  // SLIP: the env's stream, in registers for the whole loop
+    if (SLIP && mine) rng = slip_load(sl, e);
     const auto rd = [&](int cx, int cy, int &t, int &c, int &s) { cell_decode(plane[cy * g.W + cx], t, c, s); };
     const int8_t *pil = reinterpret_cast<const int8_t *>(smem + roll_pi_base(g.HWp) + lane * roll_pi_stride(r.S));
     // wave-uniform bound: until no lane is live or the budget is reached (a live lane's n equals it)
@@ -206,11 +265,14 @@ envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ 
             const int s = state_of<MODEL>(g.W, x, y, d, ct, dopen);
             const bool t_ok = r.T == 1 || (unsigned)sc < (unsigned)r.T;
             const int ln = PILDS ? pil[s] : t_ok ? r.pi[((long long)(r.T > 1 ? sc : 0) * g.B + e) * r.S + s] : -1;
-            const int a = lane_action<MODEL>(ln);
+            int a = lane_action<MODEL>(ln);
             StepOut o{};
             if (!t_ok) o.stat = MGDP_E_INVALID;
             else if (!lane_ok<MODEL>(ln)) o.stat = MGDP_E_ACTION;
-            else o = step_core(g, rd, x, y, d, sc, ct, cc, a, ms);
+            else {  // a failed lookup draws nothing; a draw is never rolled back
+                if (SLIP) a = slip_decide(rng, sl.prob, sl.random_action, a);
+                o = step_core(g, rd, x, y, d, sc, ct, cc, a, ms);
+            }
             if (o.stat != MGDP_OK) {  // the env is left as it was
                 status = o.stat;
                 live = false;
@@ -241,6 +303,7 @@ envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ 
         r.term[e] = (uint8_t)term;
         r.trunc[e] = (uint8_t)trunc;
         r.status[e] = status;
+        if (SLIP) slip_store(sl, e, rng);
     }
     if (LDS && __ballot(dirty) != 0) {  // some env of the wave changed its grid: the planes go back once
         __syncthreads();

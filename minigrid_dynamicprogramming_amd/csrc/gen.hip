@@ -7,7 +7,7 @@
 //   CROSSING   crossing.py:122-184       DOORKEY    doorkey.py:75-100
 //   LAVAGAP    lavagap.py:101-136        DISTSHIFT  distshift.py:99-121
 // with the MiniGridEnv helpers _rand_int (:242-254), place_obj (:308-367) and place_agent
-// (:378-390).  numpy's algorithms are restated below and pinned by tests against numpy itself
+// (:378-390).  numpy's algorithms are restated in pcg64.h and pinned by tests against numpy itself
 // (raw PCG64 output, Generator.integers / shuffle / choice) and against the reference's grid
 // digests (tests/golden/digests*.json):
 //   SeedSequence(entropy).generate_state(4, uint64)  -- numpy/random/bit_generator.pyx
@@ -22,135 +22,13 @@
 // x-major Grid.encode() (type, colour, state) -- the layout mgdp_envs_load takes -- and/or as
 // row-major type codes (the layout mgdp_vi_load_cells_device takes).
 #include "common.h"
+#include "pcg64.h"  // U128, seedseq_state, Pcg64: numpy's algorithms above, shared with envs.hip
 
 namespace mgdp {
 namespace {
 
 // COLOR_TO_IDX, constants.py:11-20
 enum : uint8_t { C_RED = 0, C_GREEN = 1, C_YELLOW = 4 };
-
-struct U128 {
-    uint64_t hi, lo;
-};
-
-__device__ __forceinline__ U128 mul128(U128 a, U128 b) {  // mod 2^128
-    U128 r;
-    r.lo = a.lo * b.lo;
-    r.hi = __umul64hi(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo;
-    return r;
-}
-__device__ __forceinline__ U128 add128(U128 a, U128 b) {
-    U128 r;
-    r.lo = a.lo + b.lo;
-    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1u : 0u);
-    return r;
-}
-
-// SeedSequence(seed).generate_state(4, np.uint64), pool size 4, no spawn key.
-__device__ void seedseq_state(uint64_t seed, uint64_t (&out)[4]) {
-    constexpr uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
-    constexpr uint32_t MIX_L = 0xca01f9ddu, MIX_R = 0x4973f715u;
-    uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    const int nent = (seed >> 32) ? 2 : 1;  // _int_to_uint32_array: little-endian words, 0 -> [0]
-    uint32_t hc = INIT_A;
-    auto hashmix = [&](uint32_t v) {
-        v ^= hc;
-        hc *= MULT_A;
-        v *= hc;
-        v ^= v >> 16;
-        return v;
-    };
-    auto mix = [](uint32_t x, uint32_t y) {
-        uint32_t r = MIX_L * x - MIX_R * y;
-        r ^= r >> 16;
-        return r;
-    };
-    uint32_t pool[4];
-    for (int i = 0; i < 4; ++i) pool[i] = hashmix(i < nent ? ent[i] : 0u);
-    for (int s = 0; s < 4; ++s)
-        for (int d = 0; d < 4; ++d)
-            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
-    uint32_t h = INIT_B;
-    uint32_t w[8];
-    for (int i = 0; i < 8; ++i) {
-        uint32_t v = pool[i & 3];
-        v ^= h;
-        h *= MULT_B;
-        v *= h;
-        v ^= v >> 16;
-        w[i] = v;
-    }
-    for (int i = 0; i < 4; ++i) out[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-}
-
-struct Pcg64 {
-    U128 state, inc;
-    uint32_t buf;
-    bool has32;
-
-    __device__ void step() {
-        const U128 mult{0x2360ED051FC65DA4ull, 0x4385DF649FCCF645ull};
-        state = add128(mul128(state, mult), inc);
-    }
-    __device__ explicit Pcg64(uint64_t seed) {
-        uint64_t v[4];
-        seedseq_state(seed, v);
-        const U128 initstate{v[0], v[1]}, initseq{v[2], v[3]};
-        inc = U128{(initseq.hi << 1) | (initseq.lo >> 63), (initseq.lo << 1) | 1u};
-        state = U128{0, 0};
-        step();
-        state = add128(state, initstate);
-        step();
-        has32 = false;
-        buf = 0;
-    }
-    __device__ uint64_t next64() {
-        step();
-        const uint64_t x = state.hi ^ state.lo;
-        const unsigned rot = (unsigned)(state.hi >> 58);
-        return (x >> rot) | (x << ((64u - rot) & 63u));
-    }
-    __device__ uint32_t next32() {
-        if (has32) {
-            has32 = false;
-            return buf;
-        }
-        const uint64_t n = next64();
-        has32 = true;
-        buf = (uint32_t)(n >> 32);
-        return (uint32_t)n;
-    }
-    // Generator.integers(lo, hi) (int64, hi exclusive, hi - lo <= 2^32)
-    __device__ int integers(int lo, int hi) {
-        const uint32_t rng = (uint32_t)(hi - lo - 1);
-        if (rng == 0) return lo;
-        const uint32_t excl = rng + 1u;
-        uint64_t m = (uint64_t)next32() * excl;
-        uint32_t left = (uint32_t)m;
-        if (left < excl) {
-            const uint32_t thr = (0xFFFFFFFFu - rng) % excl;
-            while (left < thr) {
-                m = (uint64_t)next32() * excl;
-                left = (uint32_t)m;
-            }
-        }
-        return lo + (int)(m >> 32);
-    }
-    // random_interval(max), the draw of Generator.shuffle on lists
-    __device__ int interval(int mx) {
-        if (mx == 0) return 0;
-        uint32_t mask = (uint32_t)mx;
-        mask |= mask >> 1;
-        mask |= mask >> 2;
-        mask |= mask >> 4;
-        mask |= mask >> 8;
-        mask |= mask >> 16;
-        uint32_t v;
-        while ((v = next32() & mask) > (uint32_t)mx) {
-        }
-        return (int)v;
-    }
-};
 
 constexpr int kGenBlock = 64;
 constexpr long long kMaxTries = 1 << 20;  // rejection cap (the reference loops without bound)

@@ -262,7 +262,8 @@ class MiniGridVecEnv:
         policy_t() (the row is step_count), or a VIResult.  A per-env problem never raises: it is that
         env's status (see RolloutResult).  trace=True records states and actions of every step taken (up
         to the envs' max_steps rows of B entries each are allocated), trace=n those of the first n steps.
-        A later call continues where this one stopped."""
+        A later call continues where this one stopped.  After set_slip() every step's action first passes
+        the env's slip stream; the trace then holds the executed actions."""
         pi, T, mid = self._policy_args(policy, model)
         B = self.num_envs
         n_max = 0 if max_steps is None else int(max_steps)
@@ -313,6 +314,57 @@ class MiniGridVecEnv:
                                              int(trace_len))
         if rc:
             _lib.check(rc, "mgdp_envs_rollout_device")
+
+    # ---------------------------------------------------------------- slip
+    def set_slip(self, prob: float = 0.9, seed: int = 0, random_action: int | None = None, mask=None):
+        """StochasticActionWrapper(env, prob, random_action) (wrappers.py:775-796) with one stream per env:
+        env b draws from numpy.random.default_rng(seed + b).  From now on every step of rollout() keeps
+        the policy's action with probability prob and otherwise executes random_action, or a uniform
+        draw of the env actions 0..5 (None).  mask (B,): reseed only those envs' streams (prob and
+        random_action always hold for the whole handle); the first call must seed them all.  step(),
+        policy_actions(), load() and reset() neither draw nor touch the streams (mgdp_envs_set_slip)."""
+        seed = int(seed)
+        if not 0 <= seed <= 2**64 - self.num_envs:
+            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
+        ra = -1 if random_action is None else int(random_action)
+        if random_action is not None and ra < 0:
+            raise ValueError(f"random_action must be an env action 0..6 or None, got {random_action}")
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
+        _lib.check(self.L.mgdp_envs_set_slip(self.h, float(prob), ra, seed, _lib.ptr(m)), "mgdp_envs_set_slip")
+
+    def clear_slip(self):
+        """Back to the plain rollout; a later set_slip seeds every stream anew."""
+        _lib.check(self.L.mgdp_envs_clear_slip(self.h), "mgdp_envs_clear_slip")
+
+    def slip_streams(self):
+        """The envs' streams as numpy's Generator.bit_generator.state holds them, one array of B entries per
+        field: {"state", "inc"}: Python ints (128 bits, object arrays), "has_uint32", "uinteger": the
+        buffered half-word.  Synchronises."""
+        B = self.num_envs
+        st = np.zeros((B, 4), np.uint64)
+        half = np.zeros((B, 2), np.uint32)
+        _lib.check(self.L.mgdp_envs_get_slip_streams(self.h, _lib.ptr(st), _lib.ptr(half)), "mgdp_envs_get_slip_streams")
+        wide = st.astype(object)
+        return {"state": (wide[:, 0] << 64) | wide[:, 1], "inc": (wide[:, 2] << 64) | wide[:, 3],
+                "has_uint32": half[:, 0].astype(np.int64), "uinteger": half[:, 1].astype(np.int64)}
+
+    def slip_actions(self, actions):
+        """(B,) int32: one slip decision per env on `actions` (mgdp_envs_slip_actions) -- what the slip
+        rollout does between the policy lookup and the step.  A negative action (policy_actions' "none")
+        passes through without a draw."""
+        a = np.ascontiguousarray(np.asarray(actions).reshape(self.num_envs), np.int32)
+        out = np.zeros(self.num_envs, np.int32)
+        _lib.check(self.L.mgdp_envs_slip_actions(self.h, _lib.ptr(a), _lib.ptr(out)), "mgdp_envs_slip_actions")
+        return out
+
+    def slip_actions_device(self, actions, out):
+        """slip_actions on device buffers (torch CUDA tensors or raw pointers), int32 (B,), asynchronous on
+        the handle's stream; out may be actions itself."""
+        rc = self.L.mgdp_envs_slip_actions_device(self.h, _lib.ptr(actions), _lib.ptr(out))
+        if rc:
+            _lib.check(rc, "mgdp_envs_slip_actions_device")
 
     def enable_timing(self, on: bool):
         """Time every step-kernel launch with a HIP event pair on the launch itself."""
