@@ -407,9 +407,57 @@ int mgdp_envs_clear_slip(mgdp_envs *envs);
 int mgdp_envs_get_slip_streams(mgdp_envs *envs, uint64_t *state, uint32_t *half);
 int mgdp_envs_slip_actions_device(mgdp_envs *envs, const int32_t *d_in, int32_t *d_out);
 int mgdp_envs_slip_actions(mgdp_envs *envs, const int32_t *in, int32_t *out);
+/* Tabular Q-learning on the resident envs, episode restarts inside the launch (DESIGN.md section 18;
+ * additive entry points, the ABI version is unchanged).  Models, state index and lanes as for the
+ * rollout above (XYD A = 7, DoorKey A = 5).  Q: fp64 [B][S][A] row-major, finite (not checked); env b
+ * reads and writes Q[b] only.  Env b explores with numpy.random.Generator(PCG64(SeedSequence(seed0 + b))),
+ * a second set of records in the layout of the slip streams, independent of them, persisting across
+ * calls.  The env's record at call entry (cells, agent, step_count, carry) is the snapshot: every
+ * episode starts there and the call leaves every env exactly as it found it -- only Q, the explore
+ * streams, the slip streams (if slip is set) and the outputs change.
+ *   Per env, n = episodes = wins = 0, ret = +0.0; an env outside the model (status MGDP_E_UNSUPPORTED, as
+ *   for the rollout) takes no step, draws nothing and keeps its Q rows.  While n < n_steps:
+ *     s = state index; u = random(); u < eps: lane = integers(0, n_act) (n_act == 1: 0, no draw), else the
+ *     lowest index attaining max Q[b][s][0..n_act) (scan from 0, replace on strict >); a = the lane's env
+ *     action, passed through one slip decision if slip is set (the update stays on the chosen lane); the
+ *     step of mgdp_envs_step with NoDeath and the front-cell mutation (MGDP_E_BOUNDS: status, the env
+ *     stops, draws are not rolled back); r = its reward, rl = (unit_goal && r > 0) ? 1.0 : r;
+ *     m = max Q[b][s'][0..n_act) read before the update; tgt = terminated ? rl : rl + gamma * m (a
+ *     truncated step bootstraps); Q[b][s][lane] = q + alpha * (tgt - q), fp64 in this order, no
+ *     contraction; n += 1, ret = ret + r; if terminated or truncated: episodes += 1,
+ *     wins += (terminated && r > 0), and the env returns to the snapshot.
+ *   The unfinished episode at the end of the budget is dropped (its updates stay): a second call
+ *   continues Q and the streams but starts at the snapshot, so calls of n1 and n2 steps equal one of
+ *   n1 + n2 only when an episode ends exactly at n1.
+ *   Trace (both pointers or neither): for the first trace_len steps s [trace_len][B] int32 and the
+ *   executed env action [trace_len][B] int8, -1 where no step was taken.
+ * Call-level refusals: MGDP_E_INVALID for n_steps <= 0, n_act outside 1..A, eps outside [0, 1] or NaN,
+ * alpha or gamma NaN, unit_goal outside {0, 1}, trace_len < 0, and q_learn before any
+ * mgdp_envs_set_explore; MGDP_E_UNSUPPORTED once Box contents planes exist, and for DoorKey on grids
+ * whose 64 padded planes do not fit a CU's LDS (the mutated plane is restored from HBM into LDS; XYD
+ * grids never mutate and run at any size).
+ *   mgdp_envs_set_explore: (re)seeds the masked explore streams (NULL: all) from seed0 + b, enqueued on
+ *     the handle's stream; the first call must seed them all (a mask is MGDP_E_INVALID).
+ *   mgdp_envs_get_explore_streams: as mgdp_envs_get_slip_streams.
+ *   mgdp_envs_q_greedy*: pi[b][s] = the lowest-index argmax of Q[b][s][0..n_act) (int8 [B][S]) and,
+ *     unless Vq is NULL, that maximum (fp64 [B][S]), for every (b, s).
+ * *_device: device pointers, asynchronous on the handle's stream.  mgdp_envs_q_learn / q_greedy take
+ * host buffers (outputs other than Q / pi may be NULL), copy Q up (and down) and synchronise. */
+int mgdp_envs_set_explore(mgdp_envs *envs, uint64_t seed0, const uint8_t *mask);
+int mgdp_envs_get_explore_streams(mgdp_envs *envs, uint64_t *state, uint32_t *half);
+int mgdp_envs_q_learn_device(mgdp_envs *envs, int32_t model, double *d_Q, int32_t n_steps, double alpha, double gamma,
+                             double eps, int32_t n_act, int32_t unit_goal, int32_t *d_steps, int32_t *d_episodes,
+                             int32_t *d_wins, double *d_ret, int32_t *d_status, int32_t *d_trace_state,
+                             int8_t *d_trace_action, int32_t trace_len);
+int mgdp_envs_q_learn(mgdp_envs *envs, int32_t model, double *Q, int32_t n_steps, double alpha, double gamma, double eps,
+                      int32_t n_act, int32_t unit_goal, int32_t *steps, int32_t *episodes, int32_t *wins, double *ret,
+                      int32_t *status, int32_t *trace_state, int8_t *trace_action, int32_t trace_len);
+int mgdp_envs_q_greedy_device(mgdp_envs *envs, int32_t model, const double *d_Q, int32_t n_act, int8_t *d_pi,
+                              double *d_Vq);
+int mgdp_envs_q_greedy(mgdp_envs *envs, int32_t model, const double *Q, int32_t n_act, int8_t *pi, double *Vq);
 /* HIP-event timing of the step kernel launches (begin/end timestamps of each dispatch, as the
- * rocprofv3 kernel trace reports them) and of the policy-lookup, slip-action and rollout launches;
- * kernel_time synchronises the stream and returns the total since enable_timing. */
+ * rocprofv3 kernel trace reports them) and of the policy-lookup, slip-action, rollout, q_learn and
+ * q_greedy launches; kernel_time synchronises the stream and returns the total since enable_timing. */
 int mgdp_envs_enable_timing(mgdp_envs *envs, int32_t on);
 int mgdp_envs_kernel_time(mgdp_envs *envs, double *total_ms, int64_t *launches);
 /* Read back env state: enc B*W*H*3 (x-major), agent B*3, carry B*2 (type,color; 0 = none),

@@ -16,6 +16,6 @@ from .minigrid_env import MiniGridEnv, MissionSpace
 from .envs import CrossingEnv, DistShiftEnv, DoorKeyEnv, EmptyEnv, FourRoomsEnv, LavaGapEnv
 from .registry import EnvSpec, make, register, registry
 from .dp import ValueIteration, VIResult, policy_evaluation, policy_iteration, value_iteration
-from .vector import MiniGridVecEnv, RolloutResult
+from .vector import MiniGridVecEnv, QLearnResult, RolloutResult
 
 __version__ = "0.1.0"

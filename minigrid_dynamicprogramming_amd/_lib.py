@@ -137,6 +137,14 @@ SIGNATURES = {
     "mgdp_envs_get_slip_streams": (ctypes.c_int, [_P, _P, _P]),
     "mgdp_envs_slip_actions_device": (ctypes.c_int, [_P, _P, _P]),
     "mgdp_envs_slip_actions": (ctypes.c_int, [_P, _P, _P]),
+    "mgdp_envs_set_explore": (ctypes.c_int, [_P, ctypes.c_uint64, _P]),
+    "mgdp_envs_get_explore_streams": (ctypes.c_int, [_P, _P, _P]),
+    "mgdp_envs_q_learn_device": (ctypes.c_int, [_P, _I32, _P, _I32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32,
+                                                _I32, _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "mgdp_envs_q_learn": (ctypes.c_int, [_P, _I32, _P, _I32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32, _I32,
+                                         _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "mgdp_envs_q_greedy_device": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P]),
+    "mgdp_envs_q_greedy": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P]),
     "mgdp_envs_enable_timing": (ctypes.c_int, [_P, _I32]),
     "mgdp_envs_kernel_time": (ctypes.c_int, [_P, _DP, _I64P]),
     "mgdp_envs_get_state": (ctypes.c_int, [_P, _P, _P, _P, _P]),

@@ -401,6 +401,7 @@ envs_step_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ age
 }
 
 #include "envs_rollout.h"  // tabular policies on resident envs: policy lookup and the fused rollout
+#include "envs_qlearn.h"   // tabular Q-learning on resident envs, episode restarts inside the launch
 
 }  // namespace mgdp
 
@@ -434,7 +435,11 @@ struct mgdp_envs {
     int slip_ra = -1;
     uint64_t *d_slip_state = nullptr;  // [B][4] state hi, lo, inc hi, lo
     uint32_t *d_slip_half = nullptr;   // [B][2] has_uint32, uinteger
-    uint8_t *d_slip_mask = nullptr;    // [B] a masked reseed's mask
+    uint8_t *d_slip_mask = nullptr;    // [B] a masked reseed's mask (slip or explore)
+    // Q-learning: the explore streams, records laid out as the slip streams'
+    bool explore = false;
+    uint64_t *d_ex_state = nullptr;
+    uint32_t *d_ex_half = nullptr;
     // step-kernel timing (mgdp_envs_enable_timing): pooled event pairs handed to hipExtLaunchKernelGGL
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
@@ -578,6 +583,72 @@ int roll_scratch(mgdp_envs *E, size_t need) {
     return 0;
 }
 
+// ---- tabular Q-learning on resident envs (envs_qlearn.h) --------------------
+SlipArgs explore_args(const mgdp_envs *E) { return SlipArgs{1.0, -1, E->d_ex_state, E->d_ex_half}; }
+
+int q_model_check(const mgdp_envs *E, int32_t model, int32_t n_act, int *S, int *A) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
+    *A = model == MGDP_MODEL_XYD ? 7 : 5;
+    *S = E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16);
+    MGDP_CHECK(n_act >= 1 && n_act <= *A, MGDP_E_INVALID, "n_act must be in 1..%d, got %d", *A, n_act);
+    return 0;
+}
+
+int q_learn_check(const mgdp_envs *E, int32_t model, int32_t n_steps, double alpha, double gamma, double eps, int32_t n_act,
+                  int32_t unit_goal, int32_t trace_len, int *S, int *A) {
+    if (int rc = q_model_check(E, model, n_act, S, A)) return rc;
+    MGDP_CHECK(n_steps > 0, MGDP_E_INVALID, "n_steps must be > 0, got %d", n_steps);
+    MGDP_CHECK(eps >= 0.0 && eps <= 1.0, MGDP_E_INVALID, "eps must be in [0, 1], got %g", eps);  // NaN fails both
+    MGDP_CHECK(alpha == alpha && gamma == gamma, MGDP_E_INVALID, "alpha and gamma must not be NaN");
+    MGDP_CHECK(unit_goal == 0 || unit_goal == 1, MGDP_E_INVALID, "unit_goal must be 0 or 1, got %d", unit_goal);
+    MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
+    MGDP_CHECK(E->explore, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
+    MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
+    MGDP_CHECK(model == MGDP_MODEL_XYD || kRollWave * roll_stride(E->HWp) <= kRollLdsMax, MGDP_E_UNSUPPORTED,
+               "DoorKey Q-learning restores mutated planes from HBM into LDS: 64 planes of %d x %d do not fit", E->W, E->H);
+    return 0;
+}
+
+using QLearnKernel = void (*)(EnvGeo, const uint8_t *, const int32_t *, const int32_t *, const int32_t *, QLearnArgs, SlipArgs,
+                              SlipArgs);
+template <bool SLIP>
+QLearnKernel qlearn_kernel(int32_t model, bool lds) {
+    return model == MGDP_MODEL_DOORKEY ? envs_qlearn_kernel<kRollDoorKey, true, SLIP>
+           : lds                       ? envs_qlearn_kernel<kRollXYD, true, SLIP>
+                                       : envs_qlearn_kernel<kRollXYD, false, SLIP>;
+}
+
+int launch_qlearn(mgdp_envs *E, int32_t model, const QLearnArgs &q) {
+    const int lds_bytes = kRollWave * roll_stride(E->HWp);
+    const bool fits = lds_bytes <= kRollLdsMax;
+    // MGDP_ROLLOUT_READER chooses the XYD reader as for the rollout; DoorKey always steps on LDS (q_learn_check)
+    const bool lds = model == MGDP_MODEL_DOORKEY || (E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits));
+    const QLearnKernel k = E->slip ? qlearn_kernel<true>(model, lds) : qlearn_kernel<false>(model, lds);
+    const int smem = lds ? lds_bytes : 0;
+    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    if (q.trace_len > 0) {  // unused entries are -1
+        MGDP_HIP(hipMemsetAsync(q.tr_state, 0xff, sizeof(int32_t) * (size_t)q.trace_len * E->B, E->stream));
+        MGDP_HIP(hipMemsetAsync(q.tr_act, 0xff, (size_t)q.trace_len * E->B, E->stream));
+    }
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
+                          E->d_cell, E->d_agent, E->d_carry, E->d_max, q, explore_args(E), slip_args(E));
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_q_greedy(mgdp_envs *E, int32_t model, int S, const double *d_Q, int32_t n_act, int8_t *d_pi, double *d_Vq) {
+    const long long n = (long long)E->B * S;
+    auto k = model == MGDP_MODEL_XYD ? envs_q_greedy_kernel<7> : envs_q_greedy_kernel<5>;
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, E->stream, ta, tb, 0, n, d_Q, n_act, d_pi, d_Vq);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -645,7 +716,7 @@ int mgdp_envs_destroy(mgdp_envs *E) {
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     void *ps[] = {E->d_cell, E->d_see, E->d_agent, E->d_carry, E->d_max, E->d_act,
                   E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage,
-                  E->d_roll, E->d_slip_state, E->d_slip_half, E->d_slip_mask};
+                  E->d_roll, E->d_slip_state, E->d_slip_half, E->d_slip_mask, E->d_ex_state, E->d_ex_half};
     for (void *p : ps) (void)hipFree(p);
     for (auto &p : E->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &p : E->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -1119,6 +1190,111 @@ int mgdp_envs_slip_actions(mgdp_envs *E, const int32_t *in, int32_t *out) {
     MGDP_HIP(hipMemcpyAsync(E->d_act, in, 4 * B, hipMemcpyHostToDevice, E->stream));
     if (int rc = launch_slip_actions(E, E->d_act, E->d_act)) return rc;
     MGDP_HIP(hipMemcpyAsync(out, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+// ---- tabular Q-learning ------------------------------------------------------
+int mgdp_envs_set_explore(mgdp_envs *E, uint64_t seed0, const uint8_t *mask) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(E->explore || !mask, MGDP_E_INVALID, "the first mgdp_envs_set_explore seeds every stream: no mask");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (!E->d_ex_state) MGDP_HIP(hipMalloc((void **)&E->d_ex_state, sizeof(uint64_t) * 4 * B));
+    if (!E->d_ex_half) MGDP_HIP(hipMalloc((void **)&E->d_ex_half, sizeof(uint32_t) * 2 * B));
+    if (mask && !E->d_slip_mask) MGDP_HIP(hipMalloc((void **)&E->d_slip_mask, B));
+    if (mask) MGDP_HIP(hipMemcpyAsync(E->d_slip_mask, mask, B, hipMemcpyHostToDevice, E->stream));
+    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
+                       mask ? E->d_slip_mask : nullptr, explore_args(E));
+    MGDP_HIP(hipGetLastError());
+    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
+    E->explore = true;
+    return 0;
+}
+
+int mgdp_envs_get_explore_streams(mgdp_envs *E, uint64_t *state, uint32_t *half) {
+    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
+    MGDP_CHECK(E->explore, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (state) MGDP_HIP(hipMemcpyAsync(state, E->d_ex_state, sizeof(uint64_t) * 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (half) MGDP_HIP(hipMemcpyAsync(half, E->d_ex_half, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, E->stream));
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int mgdp_envs_q_learn_device(mgdp_envs *E, int32_t model, double *d_Q, int32_t n_steps, double alpha, double gamma,
+                             double eps, int32_t n_act, int32_t unit_goal, int32_t *d_steps, int32_t *d_episodes,
+                             int32_t *d_wins, double *d_ret, int32_t *d_status, int32_t *d_trace_state,
+                             int8_t *d_trace_action, int32_t trace_len) {
+    int S = 0, A = 0;
+    if (int rc = q_learn_check(E, model, n_steps, alpha, gamma, eps, n_act, unit_goal, trace_len, &S, &A)) return rc;
+    MGDP_CHECK(d_Q && d_steps && d_episodes && d_wins && d_ret && d_status, MGDP_E_INVALID, "null argument");
+    const bool trace = d_trace_state && d_trace_action;
+    MGDP_CHECK(trace || (!d_trace_state && !d_trace_action), MGDP_E_INVALID, "a trace needs both of its buffers");
+    DeviceGuard guard(E->device);
+    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, trace ? trace_len : 0, alpha, gamma, eps, d_steps, d_episodes,
+                       d_wins, d_ret, d_status, trace ? d_trace_state : nullptr, trace ? d_trace_action : nullptr};
+    return launch_qlearn(E, model, q);
+}
+
+int mgdp_envs_q_learn(mgdp_envs *E, int32_t model, double *Q, int32_t n_steps, double alpha, double gamma, double eps,
+                      int32_t n_act, int32_t unit_goal, int32_t *steps, int32_t *episodes, int32_t *wins, double *ret,
+                      int32_t *status, int32_t *trace_state, int8_t *trace_action, int32_t trace_len) {
+    int S = 0, A = 0;
+    if (int rc = q_learn_check(E, model, n_steps, alpha, gamma, eps, n_act, unit_goal, trace_len, &S, &A)) return rc;
+    MGDP_CHECK(Q, MGDP_E_INVALID, "null argument");
+    const bool trace = trace_state && trace_action && trace_len > 0;
+    MGDP_CHECK(trace || (!trace_state && !trace_action) || trace_len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
+    DeviceGuard guard(E->device);
+    // scratch: Q | episodes | wins | trace states | trace actions; steps, ret and status use the step buffers
+    const size_t B = E->B, n_q = sizeof(double) * B * S * A, n_cnt = round_up(4 * B, 16), n_tr = trace ? (size_t)trace_len * B : 0;
+    if (int rc = roll_scratch(E, n_q + 2 * n_cnt + 5 * n_tr)) return rc;
+    double *d_Q = reinterpret_cast<double *>(E->d_roll);
+    int32_t *d_ep = reinterpret_cast<int32_t *>(E->d_roll + n_q);
+    int32_t *d_wn = reinterpret_cast<int32_t *>(E->d_roll + n_q + n_cnt);
+    int32_t *d_ts = reinterpret_cast<int32_t *>(E->d_roll + n_q + 2 * n_cnt);
+    int8_t *d_ta = reinterpret_cast<int8_t *>(E->d_roll + n_q + 2 * n_cnt + 4 * n_tr);
+    MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
+    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, trace ? trace_len : 0, alpha, gamma, eps, E->d_act, d_ep, d_wn,
+                       E->d_rew, E->d_status, trace ? d_ts : nullptr, trace ? d_ta : nullptr};
+    if (int rc = launch_qlearn(E, model, q)) return rc;
+    MGDP_HIP(hipMemcpyAsync(Q, d_Q, n_q, hipMemcpyDeviceToHost, E->stream));
+    if (steps) MGDP_HIP(hipMemcpyAsync(steps, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (episodes) MGDP_HIP(hipMemcpyAsync(episodes, d_ep, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (wins) MGDP_HIP(hipMemcpyAsync(wins, d_wn, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (ret) MGDP_HIP(hipMemcpyAsync(ret, E->d_rew, 8 * B, hipMemcpyDeviceToHost, E->stream));
+    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (trace) {
+        MGDP_HIP(hipMemcpyAsync(trace_state, d_ts, 4 * n_tr, hipMemcpyDeviceToHost, E->stream));
+        MGDP_HIP(hipMemcpyAsync(trace_action, d_ta, n_tr, hipMemcpyDeviceToHost, E->stream));
+    }
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int mgdp_envs_q_greedy_device(mgdp_envs *E, int32_t model, const double *d_Q, int32_t n_act, int8_t *d_pi, double *d_Vq) {
+    int S = 0, A = 0;
+    if (int rc = q_model_check(E, model, n_act, &S, &A)) return rc;
+    MGDP_CHECK(d_Q && d_pi, MGDP_E_INVALID, "null argument");
+    DeviceGuard guard(E->device);
+    return launch_q_greedy(E, model, S, d_Q, n_act, d_pi, d_Vq);
+}
+
+int mgdp_envs_q_greedy(mgdp_envs *E, int32_t model, const double *Q, int32_t n_act, int8_t *pi, double *Vq) {
+    int S = 0, A = 0;
+    if (int rc = q_model_check(E, model, n_act, &S, &A)) return rc;
+    MGDP_CHECK(Q && pi, MGDP_E_INVALID, "null argument");
+    DeviceGuard guard(E->device);
+    const size_t n = (size_t)E->B * S, n_q = sizeof(double) * n * A, n_v = sizeof(double) * n;
+    if (int rc = roll_scratch(E, n_q + n_v + n)) return rc;
+    double *d_Q = reinterpret_cast<double *>(E->d_roll);
+    double *d_V = reinterpret_cast<double *>(E->d_roll + n_q);
+    int8_t *d_pi = reinterpret_cast<int8_t *>(E->d_roll + n_q + n_v);
+    MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
+    if (int rc = launch_q_greedy(E, model, S, d_Q, n_act, d_pi, Vq ? d_V : nullptr)) return rc;
+    MGDP_HIP(hipMemcpyAsync(pi, d_pi, n, hipMemcpyDeviceToHost, E->stream));
+    if (Vq) MGDP_HIP(hipMemcpyAsync(Vq, d_V, n_v, hipMemcpyDeviceToHost, E->stream));
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }

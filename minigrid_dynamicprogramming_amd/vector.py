@@ -32,6 +32,23 @@ class RolloutResult:
         return bool((self.status == 0).all())
 
 
+@dataclass
+class QLearnResult:
+    """What MiniGridVecEnv.q_learn did, per env."""
+    Q: np.ndarray          # (B, S, A) float64 the table after the call (A: the model's lanes)
+    steps: np.ndarray      # (B,) int32 steps taken in this call (n_steps, fewer only with a status)
+    episodes: np.ndarray   # (B,) int32 episodes that ended (terminated or truncated) inside the call
+    wins: np.ndarray       # (B,) int32 those that ended on the goal (terminated with a positive reward)
+    ret: np.ndarray        # (B,) float64 the env's own rewards of every step, summed in step order
+    status: np.ndarray     # (B,) int32: 0, or the MGDP_E_* code that kept / stopped the env
+    states: np.ndarray | None = None   # trace: (n, B) int32 state index before each of the first n steps, -1 unused
+    actions: np.ndarray | None = None  # trace: (n, B) int8 env action executed at each (after the slip), -1 unused
+
+    @property
+    def ok(self) -> bool:
+        return bool((self.status == 0).all())
+
+
 class MiniGridVecEnv:
     """B independent envs of one registered id (same W, H), stepped together on one GPU.
 
@@ -81,6 +98,7 @@ class MiniGridVecEnv:
         self._next_seed = 0
         self._held = False  # Box contents planes in use (set_contents)
         self._ms_cap = self.max_steps  # the largest max_steps loaded: bounds a rollout's trace
+        self._explore = False  # the explore streams of q_learn are seeded
 
     def close(self):
         if getattr(self, "h", None):
@@ -365,6 +383,151 @@ class MiniGridVecEnv:
         rc = self.L.mgdp_envs_slip_actions_device(self.h, _lib.ptr(actions), _lib.ptr(out))
         if rc:
             _lib.check(rc, "mgdp_envs_slip_actions_device")
+
+    # ---------------------------------------------------------------- tabular Q-learning
+    def _q_model(self, model, n_act):
+        """(model name, model id, S, A, n_act) checked before any device work, in the style of _policy_args."""
+        from . import dp
+        from .envs import DoorKeyEnv
+
+        if self.autoreset:
+            raise ValueError("q_learn / q_greedy run the envs as they are: not with autoreset=True")
+        if self._held:
+            raise ValueError("Box contents (set_contents) are in use: outside the XYD and DoorKey models")
+        if model == "auto":
+            model = "doorkey" if isinstance(self._gen, DoorKeyEnv) else "xyd"
+        if model not in dp.MODELS:
+            raise ValueError(f"unknown model {model!r}")
+        S, A = dp.n_states(model, self.W, self.H), dp.n_actions(model)
+        n_act = A if n_act is None else int(n_act)
+        if not 1 <= n_act <= A:
+            raise ValueError(f"n_act must be in 1..{A} for the {model} model, got {n_act}")
+        return model, dp.MODELS[model], S, A, n_act
+
+    def _q_table(self, Q, S, A):
+        B = self.num_envs
+        if Q is None:
+            return np.zeros((B, S, A), np.float64)
+        q = np.asarray(Q)
+        if q.dtype != np.float64:
+            raise ValueError(f"Q must be float64 (fp32 tables are out of scope), got dtype {q.dtype}")
+        if q.shape != (B, S, A):
+            raise ValueError(f"Q of shape {q.shape} is not {(B, S, A)}")
+        return np.array(q, np.float64, order="C")  # the caller's table stays as it is
+
+    @staticmethod
+    def _q_params(n_steps, alpha, gamma, eps):
+        n_steps = int(n_steps)
+        if n_steps <= 0:
+            raise ValueError(f"n_steps must be > 0, got {n_steps}")
+        if n_steps >= 2**31:
+            raise ValueError("n_steps must fit int32")
+        alpha, gamma, eps = float(alpha), float(gamma), float(eps)
+        if not 0.0 <= eps <= 1.0:  # NaN fails both
+            raise ValueError(f"eps must be in [0, 1], got {eps}")
+        if alpha != alpha or gamma != gamma:
+            raise ValueError("alpha and gamma must not be NaN")
+        return n_steps, alpha, gamma, eps
+
+    def set_explore(self, seed: int = 0, mask=None):
+        """Seed the explore streams of q_learn: env b draws from numpy.random.default_rng(seed + b).  mask
+        (B,): reseed only those envs; the first call must seed them all.  Independent of the slip streams."""
+        seed = int(seed)
+        if not 0 <= seed <= 2**64 - self.num_envs:
+            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
+        _lib.check(self.L.mgdp_envs_set_explore(self.h, seed, _lib.ptr(m)), "mgdp_envs_set_explore")
+        self._explore = True
+
+    def explore_streams(self):
+        """The explore streams in the layout of slip_streams().  Synchronises."""
+        B = self.num_envs
+        st = np.zeros((B, 4), np.uint64)
+        half = np.zeros((B, 2), np.uint32)
+        _lib.check(self.L.mgdp_envs_get_explore_streams(self.h, _lib.ptr(st), _lib.ptr(half)),
+                   "mgdp_envs_get_explore_streams")
+        wide = st.astype(object)
+        return {"state": (wide[:, 0] << 64) | wide[:, 1], "inc": (wide[:, 2] << 64) | wide[:, 3],
+                "has_uint32": half[:, 0].astype(np.int64), "uinteger": half[:, 1].astype(np.int64)}
+
+    def q_learn(self, n_steps: int, Q=None, model: str = "auto", alpha: float = 0.5, gamma: float = 0.99,
+                eps: float = 0.1, n_act: int | None = None, unit_goal: bool = False, seed: int | None = None,
+                trace: bool | int = False) -> "QLearnResult":
+        """Tabular Q-learning of every env on its own table, n_steps eps-greedy steps through step() in one
+        launch (mgdp_envs_q_learn).  Q: (B, S, A) float64 in the model's state and lane order (None: zeros;
+        it is copied, the result holds the new table).  Each step: u = rng.random(); u < eps draws a lane of
+        the first n_act uniformly, else the lowest-index argmax of Q[b][s][:n_act]; then
+        Q[s][lane] += alpha * (target - Q[s][lane]) with target = r, or r + gamma * max Q[s'][:n_act] unless
+        the step terminated (unit_goal: a positive r counts as 1).  An episode that terminates or truncates
+        restarts from the env's state at the call; the call leaves every env exactly as it found it.
+        seed: env b explores with numpy.random.default_rng(seed + b); None continues the streams (seeded
+        with 0 at the first use).  After set_slip() the executed action passes the env's slip stream, the
+        update stays on the chosen lane.  A per-env problem is that env's status, never an exception.
+        trace=True records state and executed action of every step, trace=n of the first n."""
+        model, mid, S, A, n_act = self._q_model(model, n_act)
+        n_steps, alpha, gamma, eps = self._q_params(n_steps, alpha, gamma, eps)
+        q = self._q_table(Q, S, A)
+        B = self.num_envs
+        tlen = 0
+        ts = ta = None
+        if trace:
+            tlen = n_steps if trace is True else int(trace)
+            if tlen <= 0:
+                raise ValueError("trace must be True, False or a positive number of steps")
+            tlen = min(tlen, n_steps)
+            ts, ta = np.empty((tlen, B), np.int32), np.empty((tlen, B), np.int8)
+        if seed is not None:
+            self.set_explore(seed)
+        elif not self._explore:
+            self.set_explore(0)
+        steps, episodes, wins, status = (np.zeros(B, np.int32) for _ in range(4))
+        ret = np.zeros(B, np.float64)
+        p = _lib.ptr
+        _lib.check(self.L.mgdp_envs_q_learn(self.h, mid, p(q), n_steps, alpha, gamma, eps, n_act, int(bool(unit_goal)),
+                                            p(steps), p(episodes), p(wins), p(ret), p(status), p(ts), p(ta), tlen),
+                   "mgdp_envs_q_learn")
+        return QLearnResult(q, steps, episodes, wins, ret, status, ts, ta)
+
+    def q_learn_device(self, Q, n_steps: int, model: str, steps, episodes, wins, ret, status, alpha: float = 0.5,
+                       gamma: float = 0.99, eps: float = 0.1, n_act: int | None = None, unit_goal: bool = False,
+                       trace_state=None, trace_action=None, trace_len: int = 0):
+        """q_learn on device buffers (torch CUDA tensors or raw pointers), asynchronous on the handle's
+        stream: Q float64 [B][S][A] updated in place; steps / episodes / wins / status int32, ret float64, all
+        (B,); the trace int32 / int8 [trace_len][B] or None.  The explore streams must have been seeded
+        (set_explore, or an earlier q_learn)."""
+        model, mid, S, A, n_act = self._q_model(model, n_act)
+        n_steps, alpha, gamma, eps = self._q_params(n_steps, alpha, gamma, eps)
+        p = _lib.ptr
+        rc = self.L.mgdp_envs_q_learn_device(self.h, mid, p(Q), n_steps, alpha, gamma, eps, n_act, int(bool(unit_goal)),
+                                             p(steps), p(episodes), p(wins), p(ret), p(status), p(trace_state),
+                                             p(trace_action), int(trace_len))
+        if rc:
+            _lib.check(rc, "mgdp_envs_q_learn_device")
+
+    def q_greedy(self, Q, model: str = "auto", n_act: int | None = None, values: bool = False):
+        """(B, S) int8: the lowest-index argmax of Q[b][s][:n_act] for every (b, s) (mgdp_envs_q_greedy) -- a
+        policy for rollout() and ValueIteration.evaluate(); values=True also returns that maximum, (B, S)
+        float64."""
+        model, mid, S, A, n_act = self._q_model(model, n_act)
+        if Q is None:
+            raise ValueError("q_greedy needs a table")
+        q = self._q_table(Q, S, A)
+        B = self.num_envs
+        pi = np.zeros((B, S), np.int8)
+        vq = np.zeros((B, S), np.float64) if values else None
+        _lib.check(self.L.mgdp_envs_q_greedy(self.h, mid, _lib.ptr(q), n_act, _lib.ptr(pi), _lib.ptr(vq)),
+                   "mgdp_envs_q_greedy")
+        return (pi, vq) if values else pi
+
+    def q_greedy_device(self, Q, model: str, pi, values=None, n_act: int | None = None):
+        """q_greedy on device buffers, asynchronous on the handle's stream: Q float64 [B][S][A], pi int8
+        [B][S], values float64 [B][S] or None."""
+        model, mid, S, A, n_act = self._q_model(model, n_act)
+        rc = self.L.mgdp_envs_q_greedy_device(self.h, mid, _lib.ptr(Q), n_act, _lib.ptr(pi), _lib.ptr(values))
+        if rc:
+            _lib.check(rc, "mgdp_envs_q_greedy_device")
 
     def enable_timing(self, on: bool):
         """Time every step-kernel launch with a HIP event pair on the launch itself."""
