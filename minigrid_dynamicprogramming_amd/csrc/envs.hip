@@ -407,6 +407,13 @@ envs_step_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ age
 
 using namespace mgdp;
 
+// One set of per-env PCG64 records, allocated by its first seeding.
+struct StreamTable {
+    uint64_t *state = nullptr;  // [B][4] state hi, lo, inc hi, lo
+    uint32_t *half = nullptr;   // [B][2] has_uint32, uinteger
+    bool on = false;            // seeded: until then a seeding takes no mask
+};
+
 struct mgdp_envs {
     int device = 0, B = 0, W = 0, H = 0, HW = 0, HWp = 0, vs = 7;
     hipStream_t stream = nullptr;
@@ -428,18 +435,11 @@ struct mgdp_envs {
     uint8_t *d_roll = nullptr;
     size_t roll_bytes = 0;
     int roll_reader = -1;
-    bool roll_pi_lds = false;  // MGDP_ROLLOUT_PI=lds: the A/B's other side
-    // slip: per-env PCG64 records, allocated by the first mgdp_envs_set_slip
-    bool slip = false;
+    // the slip streams and Q-learning's explore streams (section 18)
+    StreamTable slip, explore;
     double slip_p = 1.0;
     int slip_ra = -1;
-    uint64_t *d_slip_state = nullptr;  // [B][4] state hi, lo, inc hi, lo
-    uint32_t *d_slip_half = nullptr;   // [B][2] has_uint32, uinteger
-    uint8_t *d_slip_mask = nullptr;    // [B] a masked reseed's mask (slip or explore)
-    // Q-learning: the explore streams, records laid out as the slip streams'
-    bool explore = false;
-    uint64_t *d_ex_state = nullptr;
-    uint32_t *d_ex_half = nullptr;
+    uint8_t *d_stream_mask = nullptr;  // [B] a masked reseed's mask (either table)
     // step-kernel timing (mgdp_envs_enable_timing): pooled event pairs handed to hipExtLaunchKernelGGL
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
@@ -508,12 +508,67 @@ int launch_step(mgdp_envs *E, const int32_t *d_act, uint8_t *d_obs, int32_t *d_d
 // ---- tabular policies on resident envs (envs_rollout.h) --------------------
 constexpr int kRollLdsMax = 160 * 1024 - 2048;  // the 64 padded planes; the rest is the staging pass's words
 
+int model_states(const mgdp_envs *E, int32_t model) { return E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16); }
+
 int roll_check(const mgdp_envs *E, int32_t model, const void *pi, int32_t T, int *S) {
     MGDP_CHECK(E && pi, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
     MGDP_CHECK(T >= 1, MGDP_E_INVALID, "T must be >= 1 (1 = a stationary policy), got %d", T);
     MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
-    *S = E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16);
+    *S = model_states(E, model);
+    return 0;
+}
+
+// The episode kernels' cell reader: LDS planes wherever a wave's 64 fit, unless MGDP_ROLLOUT_READER says hbm.
+bool roll_on_lds(const mgdp_envs *E) {
+    const bool fits = kRollWave * roll_stride(E->HWp) <= kRollLdsMax;
+    return E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits);
+}
+
+// A trace: states [len][B] and actions [len][B], or none (null, null, 0).
+struct TraceBufs {
+    int32_t *state;
+    int8_t *act;
+    int len;
+};
+
+// Device buffers: both or neither.
+int trace_device(int32_t *state, int8_t *act, int32_t len, TraceBufs *t) {
+    const bool trace = state && act;
+    MGDP_CHECK(trace || (!state && !act), MGDP_E_INVALID, "a trace needs both of its buffers");
+    *t = trace ? TraceBufs{state, act, len} : TraceBufs{nullptr, nullptr, 0};
+    return 0;
+}
+
+// Host buffers: both and len > 0, or else none is used.
+int trace_host(int32_t *state, int8_t *act, int32_t len, TraceBufs *t) {
+    const bool trace = state && act && len > 0;
+    MGDP_CHECK(trace || (!state && !act) || len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
+    *t = trace ? TraceBufs{state, act, len} : TraceBufs{nullptr, nullptr, 0};
+    return 0;
+}
+
+// One wave per 64 envs (envs_rollout_kernel, envs_qlearn_kernel): smem bytes of dynamic LDS, the trace
+// cleared to -1 (entries no step fills stay so), the launch timed like every other.  args follow the
+// env's own buffers in the kernel's signature.
+template <typename K, typename... Args>
+int launch_episode(mgdp_envs *E, K k, int smem, const TraceBufs &t, const Args &...args) {
+    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    if (t.len > 0) {
+        MGDP_HIP(hipMemsetAsync(t.state, 0xff, sizeof(int32_t) * (size_t)t.len * E->B, E->stream));
+        MGDP_HIP(hipMemsetAsync(t.act, 0xff, (size_t)t.len * E->B, E->stream));
+    }
+    hipEvent_t ta = nullptr, tb = nullptr;
+    if (int rc = timing_pair(E, ta, tb)) return rc;
+    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
+                          E->d_cell, E->d_agent, E->d_carry, E->d_max, args...);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+
+// One device-to-host copy on the handle's stream; a null dst is an output the caller did not ask for.
+int download(mgdp_envs *E, void *dst, const void *src, size_t bytes) {
+    if (dst) MGDP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, E->stream));
     return 0;
 }
 
@@ -528,39 +583,22 @@ int launch_policy_actions(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32
     return 0;
 }
 
-SlipArgs slip_args(const mgdp_envs *E) { return SlipArgs{E->slip_p, E->slip_ra, E->d_slip_state, E->d_slip_half}; }
+SlipArgs slip_args(const mgdp_envs *E) { return SlipArgs{E->slip_p, E->slip_ra, E->slip.state, E->slip.half}; }
+SlipArgs explore_args(const mgdp_envs *E) { return SlipArgs{1.0, -1, E->explore.state, E->explore.half}; }
 
 using RolloutKernel = void (*)(EnvGeo, uint8_t *, int32_t *, int32_t *, const int32_t *, RolloutArgs, SlipArgs);
 template <bool SLIP>
-RolloutKernel rollout_kernel(int32_t model, bool lds, bool pil) {
-    return model == MGDP_MODEL_XYD ? (pil   ? envs_rollout_kernel<kRollXYD, true, true, SLIP>
-                                      : lds ? envs_rollout_kernel<kRollXYD, true, false, SLIP>
-                                            : envs_rollout_kernel<kRollXYD, false, false, SLIP>)
-                                   : (pil   ? envs_rollout_kernel<kRollDoorKey, true, true, SLIP>
-                                      : lds ? envs_rollout_kernel<kRollDoorKey, true, false, SLIP>
-                                            : envs_rollout_kernel<kRollDoorKey, false, false, SLIP>);
+RolloutKernel rollout_kernel(int32_t model, bool lds) {
+    return model == MGDP_MODEL_XYD ? (lds ? envs_rollout_kernel<kRollXYD, true, SLIP> : envs_rollout_kernel<kRollXYD, false, SLIP>)
+                                   : (lds ? envs_rollout_kernel<kRollDoorKey, true, SLIP>
+                                          : envs_rollout_kernel<kRollDoorKey, false, SLIP>);
 }
 
 int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
-    const int lds_bytes = kRollWave * roll_stride(E->HWp);
-    const bool fits = lds_bytes <= kRollLdsMax;
-    const bool lds = E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits);
-    // MGDP_ROLLOUT_PI=lds: a stationary policy's rows staged too, where they fit beside the planes
-    const int pi_lds_bytes = roll_pi_base(E->HWp) + kRollWave * roll_pi_stride(r.S);
-    const bool pil = E->roll_pi_lds && lds && r.T == 1 && pi_lds_bytes <= kRollLdsMax && ((uintptr_t)r.pi & 3) == 0;
-    const RolloutKernel k = E->slip ? rollout_kernel<true>(model, lds, pil) : rollout_kernel<false>(model, lds, pil);
-    const int smem = pil ? pi_lds_bytes : lds ? lds_bytes : 0;
-    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    if (r.trace_len > 0) {  // unused entries are -1
-        MGDP_HIP(hipMemsetAsync(r.tr_state, 0xff, sizeof(int32_t) * (size_t)r.trace_len * E->B, E->stream));
-        MGDP_HIP(hipMemsetAsync(r.tr_act, 0xff, (size_t)r.trace_len * E->B, E->stream));
-    }
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
-                          E->d_cell, E->d_agent, E->d_carry, E->d_max, r, slip_args(E));
-    MGDP_HIP(hipGetLastError());
-    return 0;
+    const bool lds = roll_on_lds(E);
+    const RolloutKernel k = E->slip.on ? rollout_kernel<true>(model, lds) : rollout_kernel<false>(model, lds);
+    return launch_episode(E, k, lds ? kRollWave * roll_stride(E->HWp) : 0, TraceBufs{r.tr_state, r.tr_act, r.trace_len}, r,
+                          slip_args(E));
 }
 
 int launch_slip_actions(mgdp_envs *E, const int32_t *d_in, int32_t *d_out) {
@@ -583,14 +621,55 @@ int roll_scratch(mgdp_envs *E, size_t need) {
     return 0;
 }
 
-// ---- tabular Q-learning on resident envs (envs_qlearn.h; DESIGN.md section 18) --------------------
-SlipArgs explore_args(const mgdp_envs *E) { return SlipArgs{1.0, -1, E->d_ex_state, E->d_ex_half}; }
+// A bump allocator over d_roll: take() lays the pieces of a host call out, each from a 16-byte boundary;
+// roll_scratch(E, end) then makes d_roll hold them all, and roll_at<T>() is a piece's address.
+struct RollCursor {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t off = end;
+        end += round_up(bytes, 16);
+        return off;
+    }
+};
+template <typename T>
+T *roll_at(const mgdp_envs *E, size_t off) { return reinterpret_cast<T *>(E->d_roll + off); }
 
+// ---- stream tables: slip and explore (DESIGN.md sections 17 and 18) -------------------------------
+// Stream b of the table becomes default_rng(seed0 + b); mask [B] (host) keeps the streams of its zero
+// entries.  entry names the caller in the refusal of a masked first seeding.
+int seed_streams(mgdp_envs *E, StreamTable &t, uint64_t seed0, const uint8_t *mask, const char *entry) {
+    MGDP_CHECK(t.on || !mask, MGDP_E_INVALID, "the first %s seeds every stream: no mask", entry);
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (!t.state) MGDP_HIP(hipMalloc((void **)&t.state, sizeof(uint64_t) * 4 * B));
+    if (!t.half) MGDP_HIP(hipMalloc((void **)&t.half, sizeof(uint32_t) * 2 * B));
+    if (mask) {
+        if (!E->d_stream_mask) MGDP_HIP(hipMalloc((void **)&E->d_stream_mask, B));
+        MGDP_HIP(hipMemcpyAsync(E->d_stream_mask, mask, B, hipMemcpyHostToDevice, E->stream));
+    }
+    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
+                       mask ? E->d_stream_mask : nullptr, SlipArgs{1.0, -1, t.state, t.half});
+    MGDP_HIP(hipGetLastError());
+    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
+    t.on = true;
+    return 0;
+}
+
+int read_streams(mgdp_envs *E, const StreamTable &t, uint64_t *state, uint32_t *half) {
+    DeviceGuard guard(E->device);
+    const size_t B = E->B;
+    if (download(E, state, t.state, sizeof(uint64_t) * 4 * B) || download(E, half, t.half, sizeof(uint32_t) * 2 * B))
+        return MGDP_E_HIP;
+    MGDP_HIP(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+// ---- tabular Q-learning on resident envs (envs_qlearn.h; DESIGN.md section 18) --------------------
 int q_model_check(const mgdp_envs *E, int32_t model, int32_t n_act, int *S, int *A) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
     *A = model == MGDP_MODEL_XYD ? 7 : 5;
-    *S = E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16);
+    *S = model_states(E, model);
     MGDP_CHECK(n_act >= 1 && n_act <= *A, MGDP_E_INVALID, "n_act must be in 1..%d, got %d", *A, n_act);
     return 0;
 }
@@ -603,7 +682,7 @@ int q_learn_check(const mgdp_envs *E, int32_t model, int32_t n_steps, double alp
     MGDP_CHECK(alpha == alpha && gamma == gamma, MGDP_E_INVALID, "alpha and gamma must not be NaN");
     MGDP_CHECK(unit_goal == 0 || unit_goal == 1, MGDP_E_INVALID, "unit_goal must be 0 or 1, got %d", unit_goal);
     MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
-    MGDP_CHECK(E->explore, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
+    MGDP_CHECK(E->explore.on, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
     MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
     MGDP_CHECK(model == MGDP_MODEL_XYD || kRollWave * roll_stride(E->HWp) <= kRollLdsMax, MGDP_E_UNSUPPORTED,
                "DoorKey Q-learning restores mutated planes from HBM into LDS: 64 planes of %d x %d do not fit", E->W, E->H);
@@ -620,23 +699,11 @@ QLearnKernel qlearn_kernel(int32_t model, bool lds) {
 }
 
 int launch_qlearn(mgdp_envs *E, int32_t model, const QLearnArgs &q) {
-    const int lds_bytes = kRollWave * roll_stride(E->HWp);
-    const bool fits = lds_bytes <= kRollLdsMax;
     // MGDP_ROLLOUT_READER chooses the XYD reader as for the rollout; DoorKey always steps on LDS (q_learn_check)
-    const bool lds = model == MGDP_MODEL_DOORKEY || (E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits));
-    const QLearnKernel k = E->slip ? qlearn_kernel<true>(model, lds) : qlearn_kernel<false>(model, lds);
-    const int smem = lds ? lds_bytes : 0;
-    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    if (q.trace_len > 0) {  // unused entries are -1
-        MGDP_HIP(hipMemsetAsync(q.tr_state, 0xff, sizeof(int32_t) * (size_t)q.trace_len * E->B, E->stream));
-        MGDP_HIP(hipMemsetAsync(q.tr_act, 0xff, (size_t)q.trace_len * E->B, E->stream));
-    }
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
-                          E->d_cell, E->d_agent, E->d_carry, E->d_max, q, explore_args(E), slip_args(E));
-    MGDP_HIP(hipGetLastError());
-    return 0;
+    const bool lds = model == MGDP_MODEL_DOORKEY || roll_on_lds(E);
+    const QLearnKernel k = E->slip.on ? qlearn_kernel<true>(model, lds) : qlearn_kernel<false>(model, lds);
+    return launch_episode(E, k, lds ? kRollWave * roll_stride(E->HWp) : 0, TraceBufs{q.tr_state, q.tr_act, q.trace_len}, q,
+                          explore_args(E), slip_args(E));
 }
 
 int launch_q_greedy(mgdp_envs *E, int32_t model, int S, const double *d_Q, int32_t n_act, int8_t *d_pi, double *d_Vq) {
@@ -672,16 +739,10 @@ int mgdp_envs_create(int32_t device, int32_t B, int32_t W, int32_t H, int32_t vi
         roll_reader = !std::strcmp(ev, "hbm") ? 0 : !std::strcmp(ev, "lds") ? 1 : -2;
         MGDP_CHECK(roll_reader != -2, MGDP_E_INVALID, "MGDP_ROLLOUT_READER must be hbm or lds (got %s)", ev);
     }
-    bool roll_pi_lds = false;
-    if (const char *ev = std::getenv("MGDP_ROLLOUT_PI")) {
-        MGDP_CHECK(!std::strcmp(ev, "lds") || !std::strcmp(ev, "hbm"), MGDP_E_INVALID, "MGDP_ROLLOUT_PI must be hbm or lds (got %s)", ev);
-        roll_pi_lds = !std::strcmp(ev, "lds");
-    }
     DeviceGuard guard(device);
     mgdp_envs *E = new mgdp_envs();
     E->group = group;
     E->roll_reader = roll_reader;
-    E->roll_pi_lds = roll_pi_lds;
     E->device = device; E->B = B; E->W = W; E->H = H; E->HW = W * H; E->HWp = (int)round_up(W * H, 16);
     E->vs = view_size;
     const size_t P = (size_t)B * E->HWp;
@@ -716,7 +777,7 @@ int mgdp_envs_destroy(mgdp_envs *E) {
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     void *ps[] = {E->d_cell, E->d_see, E->d_agent, E->d_carry, E->d_max, E->d_act,
                   E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage,
-                  E->d_roll, E->d_slip_state, E->d_slip_half, E->d_slip_mask, E->d_ex_state, E->d_ex_half};
+                  E->d_roll, E->slip.state, E->slip.half, E->explore.state, E->explore.half, E->d_stream_mask};
     for (void *p : ps) (void)hipFree(p);
     for (auto &p : E->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &p : E->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -870,12 +931,10 @@ int mgdp_envs_step(mgdp_envs *E, const int32_t *actions, uint8_t *obs, int32_t *
     std::vector<int32_t> st_local;
     int32_t *stat = status;
     if (!stat) { st_local.resize(B); stat = st_local.data(); }
-    if (obs) MGDP_HIP(hipMemcpyAsync(obs, E->d_obs, B * E->vs * E->vs * 3, hipMemcpyDeviceToHost, E->stream));
-    if (direction) MGDP_HIP(hipMemcpyAsync(direction, E->d_dir, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (reward) MGDP_HIP(hipMemcpyAsync(reward, E->d_rew, 8 * B, hipMemcpyDeviceToHost, E->stream));
-    if (terminated) MGDP_HIP(hipMemcpyAsync(terminated, E->d_term, B, hipMemcpyDeviceToHost, E->stream));
-    if (truncated) MGDP_HIP(hipMemcpyAsync(truncated, E->d_trunc, B, hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipMemcpyAsync(stat, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    if (download(E, obs, E->d_obs, B * E->vs * E->vs * 3) || download(E, direction, E->d_dir, 4 * B) ||
+        download(E, reward, E->d_rew, 8 * B) || download(E, terminated, E->d_term, B) ||
+        download(E, truncated, E->d_trunc, B) || download(E, stat, E->d_status, 4 * B))
+        return MGDP_E_HIP;
     MGDP_HIP(hipStreamSynchronize(E->stream));
     for (size_t b = 0; b < B; ++b) {
         if (stat[b] == MGDP_E_ACTION) { set_error("Unknown action: %d (env %zu)", actions[b], b); return MGDP_E_ACTION; }
@@ -1081,11 +1140,10 @@ int mgdp_envs_rollout_device(mgdp_envs *E, int32_t model, const int8_t *d_pi, in
     if (int rc = roll_check(E, model, d_pi, T, &S)) return rc;
     MGDP_CHECK(d_steps && d_ret && d_terminated && d_truncated && d_status, MGDP_E_INVALID, "null argument");
     MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
-    const bool trace = d_trace_state && d_trace_action;
-    MGDP_CHECK(trace || (!d_trace_state && !d_trace_action), MGDP_E_INVALID, "a trace needs both of its buffers");
+    TraceBufs t;
+    if (int rc = trace_device(d_trace_state, d_trace_action, trace_len, &t)) return rc;
     DeviceGuard guard(E->device);
-    const RolloutArgs r{d_pi, T, S, n_max, trace ? trace_len : 0, d_steps, d_ret, d_terminated, d_truncated, d_status,
-                        trace ? d_trace_state : nullptr, trace ? d_trace_action : nullptr};
+    const RolloutArgs r{d_pi, T, S, n_max, t.len, d_steps, d_ret, d_terminated, d_truncated, d_status, t.state, t.act};
     return launch_rollout(E, model, r);
 }
 
@@ -1095,11 +1153,13 @@ int mgdp_envs_policy_actions(mgdp_envs *E, int32_t model, const int8_t *pi, int3
     MGDP_CHECK(actions, MGDP_E_INVALID, "null argument");
     DeviceGuard guard(E->device);
     const size_t B = E->B, n_pi = (size_t)T * B * S;
-    if (int rc = roll_scratch(E, n_pi)) return rc;
-    MGDP_HIP(hipMemcpyAsync(E->d_roll, pi, n_pi, hipMemcpyHostToDevice, E->stream));
-    if (int rc = launch_policy_actions(E, model, (const int8_t *)E->d_roll, T, S, E->d_act, E->d_status)) return rc;
-    MGDP_HIP(hipMemcpyAsync(actions, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
+    RollCursor c;
+    const size_t o_pi = c.take(n_pi);
+    if (int rc = roll_scratch(E, c.end)) return rc;
+    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
+    MGDP_HIP(hipMemcpyAsync(d_pi, pi, n_pi, hipMemcpyHostToDevice, E->stream));
+    if (int rc = launch_policy_actions(E, model, d_pi, T, S, E->d_act, E->d_status)) return rc;
+    if (download(E, actions, E->d_act, 4 * B) || download(E, status, E->d_status, 4 * B)) return MGDP_E_HIP;
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -1110,27 +1170,23 @@ int mgdp_envs_rollout(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, 
     int S = 0;
     if (int rc = roll_check(E, model, pi, T, &S)) return rc;
     MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
-    const bool trace = trace_state && trace_action && trace_len > 0;
-    MGDP_CHECK(trace || (!trace_state && !trace_action) || trace_len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
+    TraceBufs h;  // the caller's buffers; none: no trace is taken
+    if (int rc = trace_host(trace_state, trace_action, trace_len, &h)) return rc;
     DeviceGuard guard(E->device);
-    const size_t B = E->B, n_pi = round_up((size_t)T * B * S, 16), n_tr = trace ? (size_t)trace_len * B : 0;
-    if (int rc = roll_scratch(E, n_pi + 5 * n_tr)) return rc;
-    int32_t *d_ts = reinterpret_cast<int32_t *>(E->d_roll + n_pi);
-    int8_t *d_ta = reinterpret_cast<int8_t *>(E->d_roll + n_pi + 4 * n_tr);
-    MGDP_HIP(hipMemcpyAsync(E->d_roll, pi, (size_t)T * B * S, hipMemcpyHostToDevice, E->stream));
+    const size_t B = E->B, n_pi = (size_t)T * B * S, n_tr = (size_t)h.len * B;
+    RollCursor c;
+    const size_t o_pi = c.take(n_pi), o_ts = c.take(4 * n_tr), o_ta = c.take(n_tr);
+    if (int rc = roll_scratch(E, c.end)) return rc;
+    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
+    const TraceBufs d{roll_at<int32_t>(E, o_ts), roll_at<int8_t>(E, o_ta), h.len};
+    MGDP_HIP(hipMemcpyAsync(d_pi, pi, n_pi, hipMemcpyHostToDevice, E->stream));
     // the step entry points' per-env buffers serve as outputs: d_act holds the step counts
-    const RolloutArgs r{(const int8_t *)E->d_roll, T, S, n_max, trace ? trace_len : 0, E->d_act, E->d_rew, E->d_term,
-                        E->d_trunc, E->d_status, trace ? d_ts : nullptr, trace ? d_ta : nullptr};
+    const RolloutArgs r{d_pi, T, S, n_max, d.len, E->d_act, E->d_rew, E->d_term, E->d_trunc, E->d_status, d.state, d.act};
     if (int rc = launch_rollout(E, model, r)) return rc;
-    if (steps) MGDP_HIP(hipMemcpyAsync(steps, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (ret) MGDP_HIP(hipMemcpyAsync(ret, E->d_rew, 8 * B, hipMemcpyDeviceToHost, E->stream));
-    if (terminated) MGDP_HIP(hipMemcpyAsync(terminated, E->d_term, B, hipMemcpyDeviceToHost, E->stream));
-    if (truncated) MGDP_HIP(hipMemcpyAsync(truncated, E->d_trunc, B, hipMemcpyDeviceToHost, E->stream));
-    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (trace) {
-        MGDP_HIP(hipMemcpyAsync(trace_state, d_ts, 4 * n_tr, hipMemcpyDeviceToHost, E->stream));
-        MGDP_HIP(hipMemcpyAsync(trace_action, d_ta, n_tr, hipMemcpyDeviceToHost, E->stream));
-    }
+    if (download(E, steps, E->d_act, 4 * B) || download(E, ret, E->d_rew, 8 * B) || download(E, terminated, E->d_term, B) ||
+        download(E, truncated, E->d_trunc, B) || download(E, status, E->d_status, 4 * B) ||
+        download(E, h.state, d.state, 4 * n_tr) || download(E, h.act, d.act, n_tr))
+        return MGDP_E_HIP;
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -1141,50 +1197,34 @@ int mgdp_envs_set_slip(mgdp_envs *E, double prob, int32_t random_action, uint64_
     MGDP_CHECK(prob >= 0.0 && prob <= 1.0, MGDP_E_INVALID, "slip prob must be in [0, 1], got %g", prob);  // NaN fails both
     MGDP_CHECK(random_action >= -1 && random_action <= 6, MGDP_E_INVALID,
                "random_action must be an env action 0..6 or -1 (draw one of 0..5), got %d", random_action);
-    MGDP_CHECK(E->slip || !mask, MGDP_E_INVALID, "the first mgdp_envs_set_slip seeds every stream: no mask");
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (!E->d_slip_state) MGDP_HIP(hipMalloc((void **)&E->d_slip_state, sizeof(uint64_t) * 4 * B));
-    if (!E->d_slip_half) MGDP_HIP(hipMalloc((void **)&E->d_slip_half, sizeof(uint32_t) * 2 * B));
-    if (!E->d_slip_mask) MGDP_HIP(hipMalloc((void **)&E->d_slip_mask, B));
-    if (mask) MGDP_HIP(hipMemcpyAsync(E->d_slip_mask, mask, B, hipMemcpyHostToDevice, E->stream));
+    if (int rc = seed_streams(E, E->slip, seed0, mask, "mgdp_envs_set_slip")) return rc;
     E->slip_p = prob;
     E->slip_ra = random_action;
-    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
-                       mask ? E->d_slip_mask : nullptr, slip_args(E));
-    MGDP_HIP(hipGetLastError());
-    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
-    E->slip = true;
     return 0;
 }
 
 int mgdp_envs_clear_slip(mgdp_envs *E) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
-    E->slip = false;  // the records stay allocated; the next set_slip is a first call again
+    E->slip.on = false;  // the records stay allocated; the next set_slip is a first call again
     return 0;
 }
 
 int mgdp_envs_get_slip_streams(mgdp_envs *E, uint64_t *state, uint32_t *half) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
-    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (state) MGDP_HIP(hipMemcpyAsync(state, E->d_slip_state, sizeof(uint64_t) * 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (half) MGDP_HIP(hipMemcpyAsync(half, E->d_slip_half, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    MGDP_CHECK(E->slip.on, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    return read_streams(E, E->slip, state, half);
 }
 
 int mgdp_envs_slip_actions_device(mgdp_envs *E, const int32_t *d_in, int32_t *d_out) {
     MGDP_CHECK(E && d_in && d_out, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    MGDP_CHECK(E->slip.on, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
     DeviceGuard guard(E->device);
     return launch_slip_actions(E, d_in, d_out);
 }
 
 int mgdp_envs_slip_actions(mgdp_envs *E, const int32_t *in, int32_t *out) {
     MGDP_CHECK(E && in && out, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(E->slip, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
+    MGDP_CHECK(E->slip.on, MGDP_E_INVALID, "no slip set on this handle (mgdp_envs_set_slip)");
     DeviceGuard guard(E->device);
     const size_t B = E->B;
     MGDP_HIP(hipMemcpyAsync(E->d_act, in, 4 * B, hipMemcpyHostToDevice, E->stream));
@@ -1197,30 +1237,13 @@ int mgdp_envs_slip_actions(mgdp_envs *E, const int32_t *in, int32_t *out) {
 // ---- tabular Q-learning ------------------------------------------------------
 int mgdp_envs_set_explore(mgdp_envs *E, uint64_t seed0, const uint8_t *mask) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
-    MGDP_CHECK(E->explore || !mask, MGDP_E_INVALID, "the first mgdp_envs_set_explore seeds every stream: no mask");
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (!E->d_ex_state) MGDP_HIP(hipMalloc((void **)&E->d_ex_state, sizeof(uint64_t) * 4 * B));
-    if (!E->d_ex_half) MGDP_HIP(hipMalloc((void **)&E->d_ex_half, sizeof(uint32_t) * 2 * B));
-    if (mask && !E->d_slip_mask) MGDP_HIP(hipMalloc((void **)&E->d_slip_mask, B));
-    if (mask) MGDP_HIP(hipMemcpyAsync(E->d_slip_mask, mask, B, hipMemcpyHostToDevice, E->stream));
-    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
-                       mask ? E->d_slip_mask : nullptr, explore_args(E));
-    MGDP_HIP(hipGetLastError());
-    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
-    E->explore = true;
-    return 0;
+    return seed_streams(E, E->explore, seed0, mask, "mgdp_envs_set_explore");
 }
 
 int mgdp_envs_get_explore_streams(mgdp_envs *E, uint64_t *state, uint32_t *half) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
-    MGDP_CHECK(E->explore, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (state) MGDP_HIP(hipMemcpyAsync(state, E->d_ex_state, sizeof(uint64_t) * 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (half) MGDP_HIP(hipMemcpyAsync(half, E->d_ex_half, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    MGDP_CHECK(E->explore.on, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
+    return read_streams(E, E->explore, state, half);
 }
 
 int mgdp_envs_q_learn_device(mgdp_envs *E, int32_t model, double *d_Q, int32_t n_steps, double alpha, double gamma,
@@ -1230,11 +1253,11 @@ int mgdp_envs_q_learn_device(mgdp_envs *E, int32_t model, double *d_Q, int32_t n
     int S = 0, A = 0;
     if (int rc = q_learn_check(E, model, n_steps, alpha, gamma, eps, n_act, unit_goal, trace_len, &S, &A)) return rc;
     MGDP_CHECK(d_Q && d_steps && d_episodes && d_wins && d_ret && d_status, MGDP_E_INVALID, "null argument");
-    const bool trace = d_trace_state && d_trace_action;
-    MGDP_CHECK(trace || (!d_trace_state && !d_trace_action), MGDP_E_INVALID, "a trace needs both of its buffers");
+    TraceBufs t;
+    if (int rc = trace_device(d_trace_state, d_trace_action, trace_len, &t)) return rc;
     DeviceGuard guard(E->device);
-    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, trace ? trace_len : 0, alpha, gamma, eps, d_steps, d_episodes,
-                       d_wins, d_ret, d_status, trace ? d_trace_state : nullptr, trace ? d_trace_action : nullptr};
+    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, t.len, alpha, gamma, eps, d_steps, d_episodes,
+                       d_wins, d_ret, d_status, t.state, t.act};
     return launch_qlearn(E, model, q);
 }
 
@@ -1244,31 +1267,25 @@ int mgdp_envs_q_learn(mgdp_envs *E, int32_t model, double *Q, int32_t n_steps, d
     int S = 0, A = 0;
     if (int rc = q_learn_check(E, model, n_steps, alpha, gamma, eps, n_act, unit_goal, trace_len, &S, &A)) return rc;
     MGDP_CHECK(Q, MGDP_E_INVALID, "null argument");
-    const bool trace = trace_state && trace_action && trace_len > 0;
-    MGDP_CHECK(trace || (!trace_state && !trace_action) || trace_len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
+    TraceBufs h;  // the caller's buffers; none: no trace is taken
+    if (int rc = trace_host(trace_state, trace_action, trace_len, &h)) return rc;
     DeviceGuard guard(E->device);
     // scratch: Q | episodes | wins | trace states | trace actions; steps, ret and status use the step buffers
-    const size_t B = E->B, n_q = sizeof(double) * B * S * A, n_cnt = round_up(4 * B, 16), n_tr = trace ? (size_t)trace_len * B : 0;
-    if (int rc = roll_scratch(E, n_q + 2 * n_cnt + 5 * n_tr)) return rc;
-    double *d_Q = reinterpret_cast<double *>(E->d_roll);
-    int32_t *d_ep = reinterpret_cast<int32_t *>(E->d_roll + n_q);
-    int32_t *d_wn = reinterpret_cast<int32_t *>(E->d_roll + n_q + n_cnt);
-    int32_t *d_ts = reinterpret_cast<int32_t *>(E->d_roll + n_q + 2 * n_cnt);
-    int8_t *d_ta = reinterpret_cast<int8_t *>(E->d_roll + n_q + 2 * n_cnt + 4 * n_tr);
+    const size_t B = E->B, n_q = sizeof(double) * B * S * A, n_tr = (size_t)h.len * B;
+    RollCursor c;
+    const size_t o_q = c.take(n_q), o_ep = c.take(4 * B), o_wn = c.take(4 * B), o_ts = c.take(4 * n_tr), o_ta = c.take(n_tr);
+    if (int rc = roll_scratch(E, c.end)) return rc;
+    double *d_Q = roll_at<double>(E, o_q);
+    int32_t *d_ep = roll_at<int32_t>(E, o_ep), *d_wn = roll_at<int32_t>(E, o_wn);
+    const TraceBufs d{roll_at<int32_t>(E, o_ts), roll_at<int8_t>(E, o_ta), h.len};
     MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
-    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, trace ? trace_len : 0, alpha, gamma, eps, E->d_act, d_ep, d_wn,
-                       E->d_rew, E->d_status, trace ? d_ts : nullptr, trace ? d_ta : nullptr};
+    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, d.len, alpha, gamma, eps, E->d_act, d_ep, d_wn,
+                       E->d_rew, E->d_status, d.state, d.act};
     if (int rc = launch_qlearn(E, model, q)) return rc;
-    MGDP_HIP(hipMemcpyAsync(Q, d_Q, n_q, hipMemcpyDeviceToHost, E->stream));
-    if (steps) MGDP_HIP(hipMemcpyAsync(steps, E->d_act, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (episodes) MGDP_HIP(hipMemcpyAsync(episodes, d_ep, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (wins) MGDP_HIP(hipMemcpyAsync(wins, d_wn, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (ret) MGDP_HIP(hipMemcpyAsync(ret, E->d_rew, 8 * B, hipMemcpyDeviceToHost, E->stream));
-    if (status) MGDP_HIP(hipMemcpyAsync(status, E->d_status, 4 * B, hipMemcpyDeviceToHost, E->stream));
-    if (trace) {
-        MGDP_HIP(hipMemcpyAsync(trace_state, d_ts, 4 * n_tr, hipMemcpyDeviceToHost, E->stream));
-        MGDP_HIP(hipMemcpyAsync(trace_action, d_ta, n_tr, hipMemcpyDeviceToHost, E->stream));
-    }
+    if (download(E, Q, d_Q, n_q) || download(E, steps, E->d_act, 4 * B) || download(E, episodes, d_ep, 4 * B) ||
+        download(E, wins, d_wn, 4 * B) || download(E, ret, E->d_rew, 8 * B) || download(E, status, E->d_status, 4 * B) ||
+        download(E, h.state, d.state, 4 * n_tr) || download(E, h.act, d.act, n_tr))
+        return MGDP_E_HIP;
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -1287,14 +1304,14 @@ int mgdp_envs_q_greedy(mgdp_envs *E, int32_t model, const double *Q, int32_t n_a
     MGDP_CHECK(Q && pi, MGDP_E_INVALID, "null argument");
     DeviceGuard guard(E->device);
     const size_t n = (size_t)E->B * S, n_q = sizeof(double) * n * A, n_v = sizeof(double) * n;
-    if (int rc = roll_scratch(E, n_q + n_v + n)) return rc;
-    double *d_Q = reinterpret_cast<double *>(E->d_roll);
-    double *d_V = reinterpret_cast<double *>(E->d_roll + n_q);
-    int8_t *d_pi = reinterpret_cast<int8_t *>(E->d_roll + n_q + n_v);
+    RollCursor c;
+    const size_t o_q = c.take(n_q), o_v = c.take(n_v), o_pi = c.take(n);
+    if (int rc = roll_scratch(E, c.end)) return rc;
+    double *d_Q = roll_at<double>(E, o_q), *d_V = roll_at<double>(E, o_v);
+    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
     MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
     if (int rc = launch_q_greedy(E, model, S, d_Q, n_act, d_pi, Vq ? d_V : nullptr)) return rc;
-    MGDP_HIP(hipMemcpyAsync(pi, d_pi, n, hipMemcpyDeviceToHost, E->stream));
-    if (Vq) MGDP_HIP(hipMemcpyAsync(Vq, d_V, n_v, hipMemcpyDeviceToHost, E->stream));
+    if (download(E, pi, d_pi, n) || download(E, Vq, d_V, n_v)) return MGDP_E_HIP;
     MGDP_HIP(hipStreamSynchronize(E->stream));
     return 0;
 }

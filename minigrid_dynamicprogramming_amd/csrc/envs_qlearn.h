@@ -45,11 +45,12 @@ __device__ __forceinline__ void q_row_max(const double *row, int n_act, double &
     }
 }
 
-// The rollout's staging pass (envs_rollout.h), restated here so that the rollout kernels keep their code
-// and register figures: the wave's planes are contiguous in HBM (n_env * HWp bytes from env e0) and go
-// to LDS 16 bytes per lane and turn, at the odd-dword stride roll_stride; the model check's counts
-// and the door index are gathered per env slot on the way.  The caller's __syncthreads() makes planes
-// and counts visible.
+// The rollout's staging pass (envs_rollout.h) a second time: the wave's planes are contiguous in HBM
+// (n_env * HWp bytes from env e0) and go to LDS 16 bytes per lane and turn, at the odd-dword stride
+// roll_stride; the model check's counts and the door index are gathered per env slot on the way.  The
+// caller's __syncthreads() makes planes and counts visible.  envs_rollout_kernel keeps its inline form:
+// calling this one there leaves every resource figure alone but reorders the four LDS instantiations'
+// code, and two of their workloads then timed above the parent's spread (profiles/episode_sharing/).
 struct PlaneScanShared {
     int bad[kRollWave], ndoor[kRollWave], door[kRollWave], doorcode[kRollWave], nkey[kRollWave], keyc[kRollWave];
     __device__ __forceinline__ PlaneScan of(int l) const {

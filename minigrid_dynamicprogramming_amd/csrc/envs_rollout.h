@@ -4,7 +4,7 @@
 //   envs_policy_actions_kernel<MODEL>   one lane per env: the state index of the live env in the order
 //       of mgdp_vi_get_policy, the policy's lane there, the env action (-1: none) and a status.  No
 //       stepping: its output is what mgdp_envs_step_device takes.
-//   envs_rollout_kernel<MODEL, LDS, PILDS, SLIP>  one lane per env, one wave per workgroup: every env is carried
+//   envs_rollout_kernel<MODEL, LDS, SLIP>  one lane per env, one wave per workgroup: every env is carried
 //       through step_core until it terminates, truncates, fails or the budget ends -- no observation,
 //       no launch per step, no host in the loop.  LDS: the wave's 64 cell planes are staged into LDS
 //       with 16-byte loads (the model check and the DoorKey door index come out of the same pass), the
@@ -134,10 +134,6 @@ envs_policy_actions_kernel(EnvGeo g, const uint8_t *__restrict__ CELL, const int
 
 constexpr int kRollWave = 64;  // envs per workgroup: one wave
 __host__ __device__ inline int roll_stride(int HWp) { return HWp + 4; }
-// PILDS (the A/B of DESIGN.md section 16, MGDP_ROLLOUT_PI=lds): the wave's 64 rows of a stationary policy
-// are staged behind the planes, again at an odd dword stride (S = 4 HW or 16 HW bytes, a multiple of 4).
-__host__ __device__ inline int roll_pi_stride(int S) { return ((S >> 2) & 1) ? S : S + 4; }
-__host__ __device__ inline int roll_pi_base(int HWp) { return (kRollWave * roll_stride(HWp) + 15) & ~15; }
 
 // ---- slip streams -----------------------------------------------------------
 // Env b's record: state[4 b ..] = (state hi, state lo, inc hi, inc lo), half[2 b ..] = (has_uint32, uinteger).
@@ -191,7 +187,7 @@ envs_slip_actions_kernel(int B, SlipArgs sl, const int32_t *in, int32_t *out) {
     out[e] = a;
 }
 
-template <int MODEL, bool LDS, bool PILDS = false, bool SLIP = false>
+template <int MODEL, bool LDS, bool SLIP>
 __global__ void __launch_bounds__(kRollWave)
 envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ agent, int32_t *__restrict__ carry,
                     const int32_t *__restrict__ max_steps, RolloutArgs r, SlipArgs sl) {
@@ -226,15 +222,6 @@ envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ 
             if (q.ndoor) { atomicAdd(&s_ndoor[slot], q.ndoor); s_door[slot] = q.door; s_doorcode[slot] = q.doorcode; }
             if (q.nkey) { atomicAdd(&s_nkey[slot], q.nkey); s_keyc[slot] = q.keyc; }
         }
-        if (PILDS) {  // rows e0 .. e0+n_env-1 of pi are contiguous: n_env * S bytes, dword loads
-            const uint32_t *ps = reinterpret_cast<const uint32_t *>(r.pi + (long long)e0 * r.S);
-            const int per_row = r.S >> 2, pstride = roll_pi_stride(r.S);
-            unsigned char *pb = smem + roll_pi_base(g.HWp);
-            for (int i = lane; i < n_env * per_row; i += kRollWave) {
-                const int slot = i / per_row;
-                *reinterpret_cast<uint32_t *>(pb + slot * pstride + ((i - slot * per_row) << 2)) = ps[i];
-            }
-        }
         __syncthreads();
         p = PlaneScan{s_bad[lane], s_ndoor[lane], s_door[lane], s_doorcode[lane], s_nkey[lane], s_keyc[lane]};
         plane = smem + lane * stride;
@@ -258,13 +245,12 @@ envs_rollout_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ 
     Pcg64 rng(U128{0, 0}, U128{0, 0}, false, 0u);  // SLIP: the env's stream, in registers for the whole loop
     if (SLIP && mine) rng = slip_load(sl, e);
     const auto rd = [&](int cx, int cy, int &t, int &c, int &s) { cell_decode(plane[cy * g.W + cx], t, c, s); };
-    const int8_t *pil = reinterpret_cast<const int8_t *>(smem + roll_pi_base(g.HWp) + lane * roll_pi_stride(r.S));
     // wave-uniform bound: until no lane is live or the budget is reached (a live lane's n equals it)
     for (int it = 0; (r.n_max <= 0 || it < r.n_max) && __ballot(live) != 0; ++it) {
         if (live) {
             const int s = state_of<MODEL>(g.W, x, y, d, ct, dopen);
             const bool t_ok = r.T == 1 || (unsigned)sc < (unsigned)r.T;
-            const int ln = PILDS ? pil[s] : t_ok ? r.pi[((long long)(r.T > 1 ? sc : 0) * g.B + e) * r.S + s] : -1;
+            const int ln = t_ok ? r.pi[((long long)(r.T > 1 ? sc : 0) * g.B + e) * r.S + s] : -1;
             int a = lane_action<MODEL>(ln);
             StepOut o{};
             if (!t_ok) o.stat = MGDP_E_INVALID;

@@ -228,24 +228,32 @@ class MiniGridVecEnv:
             _lib.check(rc, "mgdp_envs_step_device")
 
     # ---------------------------------------------------------------- tabular policies
-    def _policy_args(self, policy, model):
-        """(pi int8 (T*B, S) contiguous, T, model id) of a (B, S) / (T, B, S) integer array or a VIResult,
-        checked before any device work (as ValueIteration._check_policy)."""
+    def _model_of(self, model, callers):
+        """The model's name ("auto": the generator's) for the calls that run the envs as they are, refused
+        where they cannot: autoreset, or Box contents on the handle."""
         from . import dp
         from .envs import DoorKeyEnv
 
         if self.autoreset:
-            raise ValueError("rollout / policy_actions run the envs as they are: not with autoreset=True")
+            raise ValueError(f"{callers} run the envs as they are: not with autoreset=True")
         if self._held:
             raise ValueError("Box contents (set_contents) are in use: outside the XYD and DoorKey models")
-        if isinstance(policy, dp.VIResult):
-            if model == "auto":
-                model = policy.model
-            policy = policy.pi
         if model == "auto":
             model = "doorkey" if isinstance(self._gen, DoorKeyEnv) else "xyd"
         if model not in dp.MODELS:
             raise ValueError(f"unknown model {model!r}")
+        return model
+
+    def _policy_args(self, policy, model):
+        """(pi int8 (T*B, S) contiguous, T, model id) of a (B, S) / (T, B, S) integer array or a VIResult,
+        checked before any device work (as ValueIteration._check_policy)."""
+        from . import dp
+
+        if isinstance(policy, dp.VIResult):
+            if model == "auto":
+                model = policy.model
+            policy = policy.pi
+        model = self._model_of(model, "rollout / policy_actions")
         a = np.asarray(policy)
         if a.dtype.kind not in "iu":
             raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
@@ -260,6 +268,17 @@ class MiniGridVecEnv:
         if a.ndim == 3 and T == 1:
             raise ValueError("a time-indexed policy needs T > 1 rows; pass (B, S) for a stationary one")
         return np.ascontiguousarray(a), T, dp.MODELS[model]
+
+    def _trace_arrays(self, trace, full_len, cap):
+        """(states int32 (n, B), actions int8 (n, B), n) for trace=True (n = full_len) or a number of steps,
+        at most cap rows (0: no cap); (None, None, 0) for no trace."""
+        if not trace:
+            return None, None, 0
+        n = full_len if trace is True else int(trace)
+        if n <= 0:
+            raise ValueError("trace must be True, False or a positive number of steps")
+        n = min(n, cap) if cap else n
+        return np.empty((n, self.num_envs), np.int32), np.empty((n, self.num_envs), np.int8), n
 
     def policy_actions(self, policy, model: str = "auto", return_status: bool = False):
         """(B,) int32: the env action `policy` takes at every env's current state (mgdp_envs_policy_actions),
@@ -290,14 +309,8 @@ class MiniGridVecEnv:
         steps, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
         ret = np.zeros(B, np.float64)
         term, trunc = np.zeros(B, np.uint8), np.zeros(B, np.uint8)
-        tlen = 0
-        ts = ta = None
-        if trace:  # no env outlives its max_steps from step_count 0; a budget bounds it further
-            tlen = max(int(self._ms_cap), 1) if trace is True else int(trace)
-            if tlen <= 0:
-                raise ValueError("trace must be True, False or a positive number of steps")
-            tlen = min(tlen, n_max) if n_max else tlen
-            ts, ta = np.empty((tlen, B), np.int32), np.empty((tlen, B), np.int8)
+        # no env outlives its max_steps from step_count 0; a budget bounds it further
+        ts, ta, tlen = self._trace_arrays(trace, max(int(self._ms_cap), 1), n_max)
         _lib.check(self.L.mgdp_envs_rollout(self.h, mid, _lib.ptr(pi), T, n_max, _lib.ptr(steps), _lib.ptr(ret),
                                             _lib.ptr(term), _lib.ptr(trunc), _lib.ptr(status), _lib.ptr(ts), _lib.ptr(ta),
                                             tlen), "mgdp_envs_rollout")
@@ -334,6 +347,25 @@ class MiniGridVecEnv:
             _lib.check(rc, "mgdp_envs_rollout_device")
 
     # ---------------------------------------------------------------- slip
+    def _seed_args(self, seed, mask):
+        """(seed int, mask uint8 (B,) or None) of a seeding of one stream per env, slip or explore."""
+        seed = int(seed)
+        if not 0 <= seed <= 2**64 - self.num_envs:
+            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
+        return seed, mask
+
+    def _read_streams(self, fn, name):
+        """The records that `fn` (a stream table's getter) copies out, as slip_streams() documents them."""
+        B = self.num_envs
+        st = np.zeros((B, 4), np.uint64)
+        half = np.zeros((B, 2), np.uint32)
+        _lib.check(fn(self.h, _lib.ptr(st), _lib.ptr(half)), name)
+        wide = st.astype(object)
+        return {"state": (wide[:, 0] << 64) | wide[:, 1], "inc": (wide[:, 2] << 64) | wide[:, 3],
+                "has_uint32": half[:, 0].astype(np.int64), "uinteger": half[:, 1].astype(np.int64)}
+
     def set_slip(self, prob: float = 0.9, seed: int = 0, random_action: int | None = None, mask=None):
         """StochasticActionWrapper(env, prob, random_action) (wrappers.py:775-796) with one stream per env:
         env b draws from numpy.random.default_rng(seed + b).  From now on every step of rollout() keeps
@@ -341,15 +373,10 @@ class MiniGridVecEnv:
         draw of the env actions 0..5 (None).  mask (B,): reseed only those envs' streams (prob and
         random_action always hold for the whole handle); the first call must seed them all.  step(),
         policy_actions(), load() and reset() neither draw nor touch the streams (mgdp_envs_set_slip)."""
-        seed = int(seed)
-        if not 0 <= seed <= 2**64 - self.num_envs:
-            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
+        seed, m = self._seed_args(seed, mask)
         ra = -1 if random_action is None else int(random_action)
         if random_action is not None and ra < 0:
             raise ValueError(f"random_action must be an env action 0..6 or None, got {random_action}")
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
         _lib.check(self.L.mgdp_envs_set_slip(self.h, float(prob), ra, seed, _lib.ptr(m)), "mgdp_envs_set_slip")
 
     def clear_slip(self):
@@ -360,13 +387,7 @@ class MiniGridVecEnv:
         """The envs' streams as numpy's Generator.bit_generator.state holds them, one array of B entries per
         field: {"state", "inc"}: Python ints (128 bits, object arrays), "has_uint32", "uinteger": the
         buffered half-word.  Synchronises."""
-        B = self.num_envs
-        st = np.zeros((B, 4), np.uint64)
-        half = np.zeros((B, 2), np.uint32)
-        _lib.check(self.L.mgdp_envs_get_slip_streams(self.h, _lib.ptr(st), _lib.ptr(half)), "mgdp_envs_get_slip_streams")
-        wide = st.astype(object)
-        return {"state": (wide[:, 0] << 64) | wide[:, 1], "inc": (wide[:, 2] << 64) | wide[:, 3],
-                "has_uint32": half[:, 0].astype(np.int64), "uinteger": half[:, 1].astype(np.int64)}
+        return self._read_streams(self.L.mgdp_envs_get_slip_streams, "mgdp_envs_get_slip_streams")
 
     def slip_actions(self, actions):
         """(B,) int32: one slip decision per env on `actions` (mgdp_envs_slip_actions) -- what the slip
@@ -388,16 +409,8 @@ class MiniGridVecEnv:
     def _q_model(self, model, n_act):
         """(model name, model id, S, A, n_act) checked before any device work, in the style of _policy_args."""
         from . import dp
-        from .envs import DoorKeyEnv
 
-        if self.autoreset:
-            raise ValueError("q_learn / q_greedy run the envs as they are: not with autoreset=True")
-        if self._held:
-            raise ValueError("Box contents (set_contents) are in use: outside the XYD and DoorKey models")
-        if model == "auto":
-            model = "doorkey" if isinstance(self._gen, DoorKeyEnv) else "xyd"
-        if model not in dp.MODELS:
-            raise ValueError(f"unknown model {model!r}")
+        model = self._model_of(model, "q_learn / q_greedy")
         S, A = dp.n_states(model, self.W, self.H), dp.n_actions(model)
         n_act = A if n_act is None else int(n_act)
         if not 1 <= n_act <= A:
@@ -432,25 +445,13 @@ class MiniGridVecEnv:
     def set_explore(self, seed: int = 0, mask=None):
         """Seed the explore streams of q_learn: env b draws from numpy.random.default_rng(seed + b).  mask
         (B,): reseed only those envs; the first call must seed them all.  Independent of the slip streams."""
-        seed = int(seed)
-        if not 0 <= seed <= 2**64 - self.num_envs:
-            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
+        seed, m = self._seed_args(seed, mask)
         _lib.check(self.L.mgdp_envs_set_explore(self.h, seed, _lib.ptr(m)), "mgdp_envs_set_explore")
         self._explore = True
 
     def explore_streams(self):
         """The explore streams in the layout of slip_streams().  Synchronises."""
-        B = self.num_envs
-        st = np.zeros((B, 4), np.uint64)
-        half = np.zeros((B, 2), np.uint32)
-        _lib.check(self.L.mgdp_envs_get_explore_streams(self.h, _lib.ptr(st), _lib.ptr(half)),
-                   "mgdp_envs_get_explore_streams")
-        wide = st.astype(object)
-        return {"state": (wide[:, 0] << 64) | wide[:, 1], "inc": (wide[:, 2] << 64) | wide[:, 3],
-                "has_uint32": half[:, 0].astype(np.int64), "uinteger": half[:, 1].astype(np.int64)}
+        return self._read_streams(self.L.mgdp_envs_get_explore_streams, "mgdp_envs_get_explore_streams")
 
     def q_learn(self, n_steps: int, Q=None, model: str = "auto", alpha: float = 0.5, gamma: float = 0.99,
                 eps: float = 0.1, n_act: int | None = None, unit_goal: bool = False, seed: int | None = None,
@@ -470,14 +471,7 @@ class MiniGridVecEnv:
         n_steps, alpha, gamma, eps = self._q_params(n_steps, alpha, gamma, eps)
         q = self._q_table(Q, S, A)
         B = self.num_envs
-        tlen = 0
-        ts = ta = None
-        if trace:
-            tlen = n_steps if trace is True else int(trace)
-            if tlen <= 0:
-                raise ValueError("trace must be True, False or a positive number of steps")
-            tlen = min(tlen, n_steps)
-            ts, ta = np.empty((tlen, B), np.int32), np.empty((tlen, B), np.int8)
+        ts, ta, tlen = self._trace_arrays(trace, n_steps, n_steps)
         if seed is not None:
             self.set_explore(seed)
         elif not self._explore:

@@ -498,3 +498,87 @@ def test_dp_tie(name):
     assert got.ok and got.terminated.all() and (got.ret > 0).all()
     np.testing.assert_array_equal(got.steps, c["opt_steps"])
     venv.close()
+
+
+# ---------------------------------------------------------------------------------------------- 13
+def test_masked_explore_reseed_after_a_first_seeding():
+    """set_explore(mask=...) after the streams were seeded and used: the masked envs get default_rng(seed + b),
+    the others keep their records as the learner left them."""
+    enc, agent, env = rr.grids("MiniGrid-Empty-5x5-v0", 3)
+    venv = make_venv("MiniGrid-Empty-5x5-v0", enc, agent)
+    venv.set_explore(7)
+    venv.q_learn(20)
+    before = venv.explore_streams()
+    first = sr.fresh_streams(7, 3)
+    assert all(before["state"][b] != first["state"][b] for b in range(3)), "a stream that q_learn did not advance"
+    mask = np.array([1, 0, 1], np.uint8)
+    venv.set_explore(100, mask=mask)
+    got = venv.explore_streams()
+    venv.close()
+    fresh = sr.fresh_streams(100, 3)  # env b: default_rng(100 + b)
+    for k in fresh:
+        assert got[k][0] == fresh[k][0] and got[k][2] == fresh[k][2], k
+        assert got[k][1] == before[k][1], k
+    check_streams(got, {k: np.where(mask.astype(bool), fresh[k], before[k]) for k in fresh})
+
+
+def test_one_trace_buffer_given():
+    """A trace needs both of its buffers.  The device entries refuse one alone and write nothing; the host
+    entries refuse one alone with trace_len > 0 and take no trace with trace_len == 0."""
+    import torch
+
+    INVALID = mg._lib.MGDP_E_INVALID
+    enc, agent, env = rr.grids("MiniGrid-Empty-5x5-v0", 3)
+    venv = make_venv("MiniGrid-Empty-5x5-v0", enc, agent)
+    venv.set_explore(7)
+    L, p, h = venv.L, mg._lib.ptr, venv.h
+    B, S, A, n = 3, 5 * 5 * 4, 7, 4
+    dev = torch.device("cuda", 0)
+    Q = torch.zeros((B, S, A), dtype=torch.float64, device=dev)
+    pi = torch.zeros((B, S), dtype=torch.int8, device=dev)
+    i32 = [torch.full((B,), -7, dtype=torch.int32, device=dev) for _ in range(4)]
+    ret = torch.full((B,), -7.0, dtype=torch.float64, device=dev)
+    u8 = [torch.full((B,), 9, dtype=torch.uint8, device=dev) for _ in range(2)]
+    ts = torch.full((n, B), -7, dtype=torch.int32, device=dev)
+    ta = torch.full((n, B), -7, dtype=torch.int8, device=dev)
+    torch.cuda.synchronize()
+    state0, streams0 = venv.get_state(), venv.explore_streams()
+    for s, a in ((p(ts), None), (None, p(ta))):
+        rc = L.mgdp_envs_rollout_device(h, 0, p(pi), 1, 5, p(i32[0]), p(ret), p(u8[0]), p(u8[1]), p(i32[1]), s, a, n)
+        assert rc == INVALID
+        rc = L.mgdp_envs_q_learn_device(h, 0, p(Q), 10, 0.5, 0.9, 0.1, 3, 0, p(i32[0]), p(i32[1]), p(i32[2]), p(ret),
+                                        p(i32[3]), s, a, n)
+        assert rc == INVALID
+    streams1, state1 = venv.explore_streams(), venv.get_state()  # synchronises the handle's stream
+    torch.cuda.synchronize()
+    assert not Q.any().item()
+    assert all((t == -7).all().item() for t in i32 + [ret, ts, ta]) and all((t == 9).all().item() for t in u8)
+    check_streams(streams1, streams0)
+    for k in STATE_KEYS:
+        np.testing.assert_array_equal(state1[k], state0[k], err_msg=k)
+    # the host entries
+    hQ, hpi = np.zeros((B, S, A)), np.zeros((B, S), np.int8)
+    hi32 = [np.full(B, -7, np.int32) for _ in range(4)]
+    hret = np.full(B, -7.0)
+    hu8 = [np.full(B, 9, np.uint8) for _ in range(2)]
+    hts, hta = np.full((n, B), -7, np.int32), np.full((n, B), -7, np.int8)
+
+    def rollout(s, a, tlen):
+        return L.mgdp_envs_rollout(h, 0, p(hpi), 1, 5, p(hi32[0]), p(hret), p(hu8[0]), p(hu8[1]), p(hi32[1]), s, a, tlen)
+
+    def q_learn(s, a, tlen):
+        return L.mgdp_envs_q_learn(h, 0, p(hQ), 10, 0.5, 0.9, 0.1, 3, 0, p(hi32[0]), p(hi32[1]), p(hi32[2]), p(hret),
+                                   p(hi32[3]), s, a, tlen)
+
+    for s, a in ((p(hts), None), (None, p(hta))):
+        assert rollout(s, a, n) == INVALID
+        assert q_learn(s, a, n) == INVALID
+    assert not hQ.any() and all((t == -7).all() for t in hi32 + [hret]) and all((t == 9).all() for t in hu8)
+    check_streams(venv.explore_streams(), streams0)
+    for s, a in ((p(hts), None), (None, p(hta))):
+        assert rollout(s, a, 0) == 0
+        assert (hi32[0] == 5).all() and (hi32[1] == 0).all()  # five steps each, status ok
+        assert q_learn(s, a, 0) == 0
+        assert (hi32[0] == 10).all() and (hi32[3] == 0).all()
+    assert (hts == -7).all() and (hta == -7).all()  # no trace was taken
+    venv.close()

@@ -1,8 +1,7 @@
 """The fused policy rollout against the two ways the same job was done before it, in one session:
   (a) envs_rollout_kernel: pi* of a solved handle (zero copy) rolled out to completion in one launch --
       kernel time from the handle's HIP-event timing; also with the HBM cell reader forced
-      (MGDP_ROLLOUT_READER=hbm) and with pi staged into LDS (MGDP_ROLLOUT_PI=lds), the two A/Bs of
-      DESIGN.md section 16;
+      (MGDP_ROLLOUT_READER=hbm), the A/B of DESIGN.md section 16;
   (b) the same number of envs_step_kernel launches (mgdp_envs_step_device) on the same envs with the
       rollout's own actions precomputed on the device -- the per-step path, kernel time only;
   (c) the host loop of tests/test_gpu_rollout.py (get_state, a Python state index and table lookup per
@@ -103,7 +102,7 @@ def main():
                 for k, v in old.items():
                     os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
 
-        venvs = {"lds": make(), "hbm_reader": make(MGDP_ROLLOUT_READER="hbm"), "pi_lds": make(MGDP_ROLLOUT_PI="lds")}
+        venvs = {"lds": make(), "hbm_reader": make(MGDP_ROLLOUT_READER="hbm")}
         steps = torch.zeros(B, dtype=torch.int32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
         ret = torch.zeros(B, dtype=torch.float64, device=dev)
@@ -165,10 +164,6 @@ def main():
         assert np.array_equal(host_steps, ref_steps[:Bc]), "the host loop and the rollout took different steps"
         vi.close()
         total = int(ref_steps.sum())
-        # 64 rows of pi beside the 64 planes in a CU's LDS (csrc/envs_rollout.h); where they do not fit the
-        # pi_lds side runs the default kernel and its figure is a repeat of (a)
-        S, HWp = vi.S, (vi.W * vi.H + 15) // 16 * 16
-        pi_lds_fits = 64 * (HWp + 4) + 64 * (S + 4) <= 160 * 1024 - 2048
         a, b = stats(times["lds"]), stats(times["step_device"])
         rec = {"env": env_id, "B": B, "model": model, "box": box, "reps": args.reps,
                "env_steps": total, "max_steps_per_env": n_launch, "mean_steps_per_env": round(total / B, 2),
@@ -176,8 +171,7 @@ def main():
                "a_rollout_kernel_us": a, "b_step_device_kernel_us": b, "b_launches": n_launch,
                "a_over_b": round(a["median"] / b["median"], 4),
                "a_env_steps_per_s": round(total / (a["median"] * 1e-6), 1),
-               "a_hbm_reader_kernel_us": stats(times["hbm_reader"]), "a_pi_lds_kernel_us": stats(times["pi_lds"]),
-               "pi_lds_fits": pi_lds_fits,
+               "a_hbm_reader_kernel_us": stats(times["hbm_reader"]),
                "c_host_loop_envs": Bc, "c_host_loop_wall_s": round(wall, 3), "c_host_loop_steps": n_host,
                "c_wall_us_per_env_step": round(wall * 1e6 / max(int(host_steps.sum()), 1), 3),
                "a_kernel_us_per_env_step": round(a["median"] / total, 6)}
