@@ -282,6 +282,41 @@ int mgdp_vi_improve(mgdp_vi *vi, int64_t *changed_out);
 int mgdp_vi_policy_iteration(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
                              int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out);
 
+/* The same under the handle options (additive entry points, the ABI version is
+ * unchanged): the entry points above keep refusing a handle with horizon > 0 or MGDP_LAVA_NODEATH,
+ * these accept it.  On a plain handle each gives exactly the result of the entry point it mirrors
+ * (evaluate_opts with T = 1 and no V_t: mgdp_vi_evaluate / mgdp_vi_evaluate_device; improve_opts:
+ * mgdp_vi_improve; policy_iteration_opts: mgdp_vi_policy_iteration).  Handle rules as above: the
+ * evaluation owns the protocol state until mgdp_vi_reset, mgdp_vi_solve resets and behaves as before,
+ * mgdp_vi_kernel_time counts the launches.
+ *   NoDeath lava, horizon 0: mgdp_vi_evaluate's discounted V^pi on the NoDeath tables (lava cells are
+ *     states, entering lava gives R = death_cost and does not terminate; V may be negative), the same
+ *     global stopping rule, fixed-point completion and grid_sweeps contract.  T must be 1, V_t NULL.
+ *   horizon H > 0 (XYD or DoorKey, with or without slip / NoDeath): backward induction, exactly H
+ *     sweeps: V_H = 0, V_t[s] = Q_t[s, pi_t(s)] (or the slip mix) with the goal reward _reward(t+1, H) of
+ *     the solve.  pi is stationary (T = 1, [B][S], pi_t = pi) or time-indexed (T = H, [H][B][S], t-major:
+ *     the layout of mgdp_vi_get_policy_t and of mgdp_envs_rollout); any other T is MGDP_E_INVALID.
+ *     Results: mgdp_vi_get_values V_0, sweeps H, converged 1, every grid_sweeps entry H, dv the last
+ *     sweep's max|V_0 - V_1| (as the horizon solve reports it), mgdp_vi_get_policy the normalised pi_0.
+ *     V_t (nullable): every V_t, t = 0..H-1, as float / double [H][B][S], t-major.
+ *     A lane outside [0, A) on a valid state, in any row, is MGDP_E_INVALID; the message names the
+ *     lowest offending grid, within it the largest offending t (the first row the backward induction
+ *     reaches) and within that row the lowest offending state; that grid sweeps nothing further and
+ *     the handle stays usable.
+ *   mgdp_vi_evaluate_opts_device: policy and V_t in device memory (16-byte aligned, complete before
+ *     the call); d_pi NULL evaluates the handle's own pi (T = 1) or pi_t (T = H, needs
+ *     MGDP_KEEP_POLICY_T: pi_t* right after a solve reproduces the solve's V_0).
+ *   mgdp_vi_improve_opts / mgdp_vi_policy_iteration_opts: mgdp_vi_improve / mgdp_vi_policy_iteration on
+ *     the NoDeath Q (keep-current tie rule, lowest index otherwise); horizon 0 only -- on a finite
+ *     horizon both are MGDP_E_UNSUPPORTED (its greedy step is the solve itself). */
+int mgdp_vi_evaluate_opts(mgdp_vi *vi, const int8_t *pi, int32_t T, void *V_t, int32_t *sweeps_out, double *dv_out,
+                          int32_t *converged_out);
+int mgdp_vi_evaluate_opts_device(mgdp_vi *vi, const int8_t *d_pi, int32_t T, void *d_V_t, int32_t *sweeps_out,
+                                 double *dv_out, int32_t *converged_out);
+int mgdp_vi_improve_opts(mgdp_vi *vi, int64_t *changed_out);
+int mgdp_vi_policy_iteration_opts(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
+                                  int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out);
+
 /* Results (host).  V: B*S of float or double per dtype; pi: B*S int8 (-1 = absorbing state). */
 int mgdp_vi_get_values(mgdp_vi *vi, void *V);
 int mgdp_vi_get_policy(mgdp_vi *vi, int8_t *pi);

@@ -5,6 +5,8 @@ Hot path (HIP, gfx950, libmgdp.so behind include/mgdp.h):
   * Jacobi value iteration over (pos, dir[, has_key, door_open]) (csrc/vi.hip)
   * policy evaluation (V^pi of a given policy), greedy improvement and policy iteration on the
     same model and stopping rule                              (csrc/vi_eval.h)
+  * the same under NoDeath lava and finite horizons: V_0 and every V_t of a stationary or
+    time-indexed policy in exactly H sweeps                   (csrc/vi_eval_opts.h)
   * tabular policies executed on resident envs: policy lookup and the fused rollout, many steps
     of every env in one launch                                (csrc/envs_rollout.h)
 Host side (this package): the reference's env API, registry and grid generators, the DP front end

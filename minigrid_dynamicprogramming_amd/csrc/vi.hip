@@ -25,6 +25,9 @@
 //                     LDS tile of the neighbourhood), updated from LDS, written back.
 //   vi_eval_kernel / vi_improve_kernel (vi_eval.h)  policy evaluation under the same protocol, and the
 //                     greedy improvement step.
+//   vi_eval_fh_kernel / vi_eval_nd_kernel / vi_improve_nd_kernel (vi_eval_opts.h)  the same under the
+//                     handle options: finite-horizon backward induction of a stationary or time-indexed
+//                     policy, and evaluation / improvement on NoDeath lava.
 // Device code is split into vi_model.h (model), vi_loops.h (workgroup loops), vi_kernels.h
 // (kernels); this file holds the host side and the C ABI.  Which loop a handle runs is decided once,
 // in vi_plan.h (host-plain: plan_vi); vi_layout.h holds the LDS sizes host and device share.
@@ -53,6 +56,7 @@
 #include "vi_loops.h"
 #include "vi_kernels.h"
 #include "vi_eval.h"
+#include "vi_eval_opts.h"
 
 
 // ================================================================================================
@@ -144,6 +148,10 @@ struct mgdp_vi {
     // at the first evaluation; `evaluated`: kenv / dvenv / V are an evaluation's (cleared by mgdp_vi_reset)
     unsigned long long *d_eval = nullptr;
     bool evaluated = false;
+    // mgdp_vi_evaluate_opts (vi_eval_opts.h): device staging of a host time-indexed policy [H][B][S] and
+    // of the host V_t output T [H][B][S], allocated at the first call that needs them
+    int8_t *d_pi_stage = nullptr;
+    void *d_vt_stage = nullptr;
 };
 
 namespace {
@@ -990,6 +998,8 @@ int mgdp_vi_destroy(mgdp_vi *vi) {
     (void)hipFree(vi->d_rgoal);
     (void)hipFree(vi->d_pi_t);
     (void)hipFree(vi->d_eval);
+    (void)hipFree(vi->d_pi_stage);
+    (void)hipFree(vi->d_vt_stage);
     if (vi->h_out) (void)hipHostFree(vi->h_out);
     if (vi->h_stage) (void)hipHostFree(vi->h_stage);
     if (vi->own_stream) (void)hipStreamDestroy(vi->stream);
@@ -1608,7 +1618,46 @@ int launch_eval_m(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
     return vi->d.slip_p >= 0.0 ? launch_eval_t<T, MGDP_MODEL_XYD, true>(vi, k_target, pi_src)
                                : launch_eval_t<T, MGDP_MODEL_XYD, false>(vi, k_target, pi_src);
 }
+// NoDeath lava (reached through the *_opts entry points only): vi_eval_nd_kernel under the same protocol
+template <typename T, bool SLIP>
+int launch_eval_nd_t(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    auto kern = vi_eval_nd_kernel<T, SLIP>;
+    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
+    TimedPair tp;
+    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
+                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
+                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, k_target, vi->fresh,
+                          vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
+    MGDP_HIP(hipGetLastError());
+    vi->fresh = 0;
+    if (vi->d.B > vi->kn.inkernel_max) {
+        launch_reduce(vi, vi->d_hout);
+        MGDP_HIP(hipGetLastError());
+    }
+    return 0;
+}
+template <typename T>
+int launch_eval_nd(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    return vi->d.slip_p >= 0.0 ? launch_eval_nd_t<T, true>(vi, k_target, pi_src) : launch_eval_nd_t<T, false>(vi, k_target, pi_src);
+}
+template <typename T, bool SLIP>
+int launch_improve_nd_t(mgdp_vi *vi) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    hipLaunchKernelGGL((vi_improve_nd_kernel<T, SLIP>), dim3(vi->d.B), dim3(s.improve_block), s.improve_lds, vi->stream,
+                       eval_geo(vi, s), make_coef<T>(vi), vi->d_cells, (const T *)vi->d_V[0], vi->d_pi, vi->d_eval + 1);
+    MGDP_HIP(hipGetLastError());
+    return 0;
+}
+template <typename T>
+int launch_improve_nd(mgdp_vi *vi) {
+    return vi->d.slip_p >= 0.0 ? launch_improve_nd_t<T, true>(vi) : launch_improve_nd_t<T, false>(vi);
+}
+
 int launch_eval(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+    if (vi->d.lava_mode == MGDP_LAVA_NODEATH)
+        return vi->d.dtype == MGDP_F32 ? launch_eval_nd<float>(vi, k_target, pi_src) : launch_eval_nd<double>(vi, k_target, pi_src);
     return vi->d.dtype == MGDP_F32 ? launch_eval_m<float>(vi, k_target, pi_src) : launch_eval_m<double>(vi, k_target, pi_src);
 }
 template <typename T>
@@ -1665,11 +1714,134 @@ int eval_run(mgdp_vi *vi, const int8_t *d_src, int32_t *sweeps_out, double *dv_o
 int improve_run(mgdp_vi *vi, int64_t *changed_out) {
     if (int rc = eval_buffers(vi)) return rc;
     MGDP_HIP(hipMemsetAsync(vi->d_eval + 1, 0, sizeof(unsigned long long), vi->stream));
-    if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_m<float>(vi) : launch_improve_m<double>(vi)) return rc;
+    if (vi->d.lava_mode == MGDP_LAVA_NODEATH) {
+        if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_nd<float>(vi) : launch_improve_nd<double>(vi)) return rc;
+    } else if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_m<float>(vi) : launch_improve_m<double>(vi)) {
+        return rc;
+    }
     unsigned long long n = 0;
     MGDP_HIP(hipMemcpyAsync(&n, vi->d_eval + 1, sizeof(n), hipMemcpyDeviceToHost, vi->stream));
     MGDP_HIP(hipStreamSynchronize(vi->stream));
     if (changed_out) *changed_out = (int64_t)n;
+    return 0;
+}
+
+int policy_iteration_run(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out, int64_t *eval_sweeps_out,
+                         int64_t *changed_out, double *dv_out) {
+    const size_t BS = (size_t)vi->d.B * vi->S;
+    if (pi0) {
+        MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi0, BS, hipMemcpyHostToDevice, vi->stream));
+        MGDP_HIP(hipStreamSynchronize(vi->stream));
+    } else {  // "forward" everywhere; the evaluation stores -1 on absorbing states
+        MGDP_HIP(hipMemsetAsync(vi->d_pi, 2, BS, vi->stream));
+    }
+    int32_t iters = 0, k = 0;
+    int64_t total = 0, changed = 0;
+    double dv = 0.0;
+    do {
+        if (int rc = eval_run(vi, vi->d_pi, &k, &dv, nullptr)) return rc;
+        if (int rc = improve_run(vi, &changed)) return rc;
+        total += k;
+        ++iters;
+    } while (changed != 0 && iters < max_iters);
+    if (iters_out) *iters_out = iters;
+    if (eval_sweeps_out) *eval_sweeps_out = total;
+    if (changed_out) *changed_out = changed;
+    if (dv_out) *dv_out = dv;
+    return 0;
+}
+
+// ---- evaluation under the handle options (kernels in vi_eval_opts.h) ----
+inline bool option_handle(const mgdp_vi *vi) { return vi->d.horizon > 0 || vi->d.lava_mode != MGDP_LAVA_TERMINAL; }
+
+int eval_opts_supported(const mgdp_vi *vi, const char *what) {
+    MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
+    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED, MGDP_E_UNSUPPORTED, "%s runs on the fused method only", what);
+    MGDP_CHECK(vi->HW <= 1024, MGDP_E_UNSUPPORTED, "%s under horizon / lava options needs W*H <= 1024", what);
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    MGDP_CHECK(s.lds <= 160 * 1024, MGDP_E_UNSUPPORTED,
+               "%s: grid too large for the LDS-resident evaluation (%d B > 160 KiB)", what, s.lds);
+    MGDP_CHECK(vi->d.horizon <= kFhMaxH && vi->d.B <= kFhMaxB, MGDP_E_UNSUPPORTED,
+               "%s: horizon %d / batch %d exceed the policy error word", what, vi->d.horizon, vi->d.B);
+    return 0;
+}
+
+template <typename T, int MODEL, bool SLIP, bool ND, bool TI, bool VT>
+int launch_eval_fh_v(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    auto kern = vi_eval_fh_kernel<T, MODEL, SLIP, ND, TI, VT>;
+    constexpr int max_block = kEvalFhBlock<T, MODEL>;
+    MGDP_CHECK(s.block <= max_block, MGDP_E_UNSUPPORTED, "policy evaluation: %d cell slots exceed the kernel's %d threads",
+               s.block, max_block);
+    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
+    TimedPair tp;
+    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
+                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
+                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, (const T *)vi->d_rgoal, (T *)d_vt,
+                          vi->d.horizon, vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
+    MGDP_HIP(hipGetLastError());
+    vi->fresh = 0;
+    if (vi->d.B > vi->kn.inkernel_max) {
+        launch_reduce(vi, vi->d_hout);
+        MGDP_HIP(hipGetLastError());
+    }
+    return 0;
+}
+template <typename T, int MODEL, bool SLIP, bool ND, bool TI>
+int launch_eval_fh_t(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
+    return d_vt ? launch_eval_fh_v<T, MODEL, SLIP, ND, TI, true>(vi, pi_src, d_vt)
+                : launch_eval_fh_v<T, MODEL, SLIP, ND, TI, false>(vi, pi_src, d_vt);
+}
+template <typename T, bool TI>
+int launch_eval_fh_m(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
+    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_eval_fh_t<T, MGDP_MODEL_DOORKEY, false, false, TI>(vi, pi_src, d_vt);
+    const bool slip = vi->d.slip_p >= 0.0, nd = vi->d.lava_mode == MGDP_LAVA_NODEATH;
+    if (slip) return nd ? launch_eval_fh_t<T, MGDP_MODEL_XYD, true, true, TI>(vi, pi_src, d_vt)
+                        : launch_eval_fh_t<T, MGDP_MODEL_XYD, true, false, TI>(vi, pi_src, d_vt);
+    return nd ? launch_eval_fh_t<T, MGDP_MODEL_XYD, false, true, TI>(vi, pi_src, d_vt)
+              : launch_eval_fh_t<T, MGDP_MODEL_XYD, false, false, TI>(vi, pi_src, d_vt);
+}
+int launch_eval_fh(mgdp_vi *vi, const int8_t *pi_src, bool ti, void *d_vt) {
+    if (vi->d.dtype == MGDP_F32) return ti ? launch_eval_fh_m<float, true>(vi, pi_src, d_vt) : launch_eval_fh_m<float, false>(vi, pi_src, d_vt);
+    return ti ? launch_eval_fh_m<double, true>(vi, pi_src, d_vt) : launch_eval_fh_m<double, false>(vi, pi_src, d_vt);
+}
+
+// The finite-horizon evaluation of the policy at d_src (T rows: 1 or H), one launch of exactly H sweeps.
+int eval_fh_run(mgdp_vi *vi, const int8_t *d_src, int T, void *d_vt, int32_t *sweeps_out, double *dv_out,
+                int32_t *converged_out) {
+    const int H = vi->d.horizon;
+    if (!vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi))
+        if (int rc = learn_dispatch(vi)) return rc;
+    if (int rc = eval_buffers(vi)) return rc;
+    MGDP_HIP(hipMemsetAsync(vi->d_eval, 0xff, sizeof(unsigned long long), vi->stream));
+    vi->fresh = 1;
+    vi->cur = 0;
+    vi->k_done = vi->k_min = 0;
+    vi->k_done_valid = false;
+    vi->sweeps = vi->converged = 0;
+    vi->evaluated = true;  // whatever follows, kenv / dvenv / V are no longer a solve's
+    int32_t k = 0;
+    double dv = 0.0;
+    if (int rc = launch_eval_fh(vi, d_src, T != 1, d_vt)) return rc;
+    if (int rc = reduce_env(vi, &k, &dv)) return rc;
+    unsigned long long err = kEvalNoError;
+    MGDP_HIP(hipMemcpyAsync(&err, vi->d_eval, sizeof(err), hipMemcpyDeviceToHost, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));
+    vi->k_done_valid = false;
+    if (err != kEvalNoError) {
+        const int row = (int)((err >> kFhRowShift) & (unsigned long long)(kFhMaxH - 1));
+        MGDP_CHECK(false, MGDP_E_INVALID, "policy: grid %d t %d state %d: action %d is outside [0, %d)",
+                   (int)(err >> kFhGridShift), T == 1 ? 0 : H - 1 - row, (int)((err >> 8) & 0x3fffu),
+                   (int)(int8_t)(err & 0xffu), vi->A);
+    }
+    MGDP_CHECK(k == H && vi->k_min == H, MGDP_E_INVALID, "evaluate: the horizon's %d sweeps ended at %d..%d", H, vi->k_min, k);
+    vi->k_done = k;
+    vi->sweeps = k;
+    vi->converged = 1;  // a finite horizon is exact after H sweeps
+    if (sweeps_out) *sweeps_out = k;
+    if (dv_out) *dv_out = dv;
+    if (converged_out) *converged_out = 1;
     return 0;
 }
 }  // namespace
@@ -1710,27 +1882,82 @@ int mgdp_vi_policy_iteration(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, 
     if (int rc = eval_supported(vi, "policy iteration")) return rc;
     DeviceGuard guard(vi->d.device);
     if (int rc = server_stop(vi)) return rc;
+    return policy_iteration_run(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
+}
+
+int mgdp_vi_evaluate_opts_device(mgdp_vi *vi, const int8_t *d_pi, int32_t T, void *d_V_t, int32_t *sweeps_out,
+                                 double *dv_out, int32_t *converged_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    const int H = vi->d.horizon;
+    MGDP_CHECK(T == 1 || (H > 0 && T == H), MGDP_E_INVALID,
+               "policy rows T = %d: 1 (stationary)%s", T, H > 0 ? " or the handle's horizon" : " on a horizon-0 handle");
+    MGDP_CHECK(!(d_V_t && H == 0), MGDP_E_INVALID, "V_t needs a finite horizon");
+    if (!option_handle(vi)) return mgdp_vi_evaluate_device(vi, d_pi, sweeps_out, dv_out, converged_out);
+    if (int rc = eval_opts_supported(vi, "policy evaluation")) return rc;
+    MGDP_CHECK((((uintptr_t)d_pi | (uintptr_t)d_V_t) & 15u) == 0, MGDP_E_INVALID,
+               "policy / V_t: the device pointers must be 16-byte aligned");
+    MGDP_CHECK(d_pi || T == 1 || vi->d_pi_t, MGDP_E_INVALID,
+               "no per-step policy on the handle: create with MGDP_KEEP_POLICY_T, or pass pi");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    const int8_t *src = d_pi ? d_pi : (T == 1 ? vi->d_pi : vi->d_pi_t);
+    if (H == 0) return eval_run(vi, src, sweeps_out, dv_out, converged_out);
+    return eval_fh_run(vi, src, T, d_V_t, sweeps_out, dv_out, converged_out);
+}
+
+int mgdp_vi_evaluate_opts(mgdp_vi *vi, const int8_t *pi, int32_t T, void *V_t, int32_t *sweeps_out, double *dv_out,
+                          int32_t *converged_out) {
+    MGDP_CHECK(vi && pi, MGDP_E_INVALID, "null argument");
+    const int H = vi->d.horizon;
+    MGDP_CHECK(T == 1 || (H > 0 && T == H), MGDP_E_INVALID,
+               "policy rows T = %d: 1 (stationary)%s", T, H > 0 ? " or the handle's horizon" : " on a horizon-0 handle");
+    MGDP_CHECK(!(V_t && H == 0), MGDP_E_INVALID, "V_t needs a finite horizon");
+    if (!option_handle(vi)) return mgdp_vi_evaluate(vi, pi, sweeps_out, dv_out, converged_out);
+    if (int rc = eval_opts_supported(vi, "policy evaluation")) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
     const size_t BS = (size_t)vi->d.B * vi->S;
-    if (pi0) {
-        MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi0, BS, hipMemcpyHostToDevice, vi->stream));
-        MGDP_HIP(hipStreamSynchronize(vi->stream));
-    } else {  // "forward" everywhere; the evaluation stores -1 on absorbing states
-        MGDP_HIP(hipMemsetAsync(vi->d_pi, 2, BS, vi->stream));
+    int8_t *dst = vi->d_pi;
+    if (T != 1) {
+        if (!vi->d_pi_stage) MGDP_HIP(hipMalloc((void **)&vi->d_pi_stage, (size_t)H * BS));
+        dst = vi->d_pi_stage;
     }
-    int32_t iters = 0, k = 0;
-    int64_t total = 0, changed = 0;
-    double dv = 0.0;
-    do {
-        if (int rc = eval_run(vi, vi->d_pi, &k, &dv, nullptr)) return rc;
-        if (int rc = improve_run(vi, &changed)) return rc;
-        total += k;
-        ++iters;
-    } while (changed != 0 && iters < max_iters);
-    if (iters_out) *iters_out = iters;
-    if (eval_sweeps_out) *eval_sweeps_out = total;
-    if (changed_out) *changed_out = changed;
-    if (dv_out) *dv_out = dv;
+    if (V_t && !vi->d_vt_stage) MGDP_HIP(hipMalloc(&vi->d_vt_stage, (size_t)H * BS * vi->tsize));
+    MGDP_HIP(hipMemcpyAsync(dst, pi, (size_t)T * BS, hipMemcpyHostToDevice, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));  // the caller's buffer is free when this returns
+    if (H == 0) return eval_run(vi, dst, sweeps_out, dv_out, converged_out);
+    if (int rc = eval_fh_run(vi, dst, T, V_t ? vi->d_vt_stage : nullptr, sweeps_out, dv_out, converged_out)) return rc;
+    if (V_t) {
+        MGDP_HIP(hipMemcpyAsync(V_t, vi->d_vt_stage, (size_t)H * BS * vi->tsize, hipMemcpyDeviceToHost, vi->stream));
+        MGDP_HIP(hipStreamSynchronize(vi->stream));
+    }
     return 0;
+}
+
+int mgdp_vi_improve_opts(mgdp_vi *vi, int64_t *changed_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    if (!option_handle(vi)) return mgdp_vi_improve(vi, changed_out);
+    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED,
+               "policy improvement is refused on a finite horizon: its greedy step is the solve itself");
+    if (int rc = eval_opts_supported(vi, "policy improvement")) return rc;
+    MGDP_CHECK(vi->sweeps > 0, MGDP_E_INVALID, "policy improvement: no value function (solve or evaluate first)");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    return improve_run(vi, changed_out);
+}
+
+int mgdp_vi_policy_iteration_opts(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
+                                  int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    if (!option_handle(vi))
+        return mgdp_vi_policy_iteration(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
+    MGDP_CHECK(max_iters > 0, MGDP_E_INVALID, "max_iters must be > 0");
+    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED,
+               "policy iteration is refused on a finite horizon: its greedy step is the solve itself");
+    if (int rc = eval_opts_supported(vi, "policy iteration")) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    return policy_iteration_run(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
 }
 
 int mgdp_vi_solve_last(mgdp_vi *vi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {

@@ -346,6 +346,91 @@ class ValueIteration:
         self.sweeps = int(self.grid_sweeps().max())
         return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
 
+    # -- the same under horizon / lava="nodeath" 
+    def _check_policy_opts(self, pi) -> tuple[np.ndarray, int]:
+        """(B, S) or (H, B, S) int8 action lanes, checked before any device work: (array, rows T)."""
+        a = np.asarray(pi)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
+        if a.shape == (self.B, self.S):
+            T = 1
+        elif self.horizon > 0 and a.shape == (self.horizon, self.B, self.S):
+            T = self.horizon
+        else:
+            want = f"{(self.B, self.S)}" + (f" or {(self.horizon, self.B, self.S)}" if self.horizon > 0 else "")
+            raise ValueError(f"policy of shape {a.shape} does not match the handle's {want}")
+        if a.dtype != np.int8:
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError("policy entries do not fit int8 action lanes")
+            a = a.astype(np.int8)
+        return np.ascontiguousarray(a), T
+
+    def evaluate_opts(self, pi, values_t: bool = False) -> int:
+        """evaluate() on any handle (mgdp_vi_evaluate_opts).  lava="nodeath", horizon 0: the discounted
+        V^pi on the NoDeath tables.  horizon H > 0: backward induction, exactly H sweeps, of a stationary
+        (B, S) or time-indexed (H, B, S) policy (policy_t()'s layout, the row is step_count before the
+        step); values() is then V_0, policy() the normalised pi_0, and with values_t=True values_t()
+        returns every V_t as (H, B, S).  A lane outside [0, A) on a valid state, in any row, raises
+        ValueError naming grid, t and state.  On a plain handle: exactly evaluate().  Returns the sweeps."""
+        a, T = self._check_policy_opts(pi)
+        if values_t and self.horizon == 0:
+            raise ValueError("values_t needs a finite horizon")
+        vt = np.empty((self.horizon, self.B, self.S), self.np_dtype) if values_t else None
+        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
+        self._values_t = None
+        _lib.check(self.L.mgdp_vi_evaluate_opts(self.h, _lib.ptr(a), T, None if vt is None else _lib.ptr(vt),
+                                                ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
+                   "mgdp_vi_evaluate_opts")
+        self._values_t = vt
+        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
+        return self.sweeps
+
+    def values_t(self) -> np.ndarray:
+        """(H, B, S): every V_t of the last evaluate_opts(pi, values_t=True)."""
+        vt = getattr(self, "_values_t", None)
+        if vt is None:
+            raise ValueError("no V_t: call evaluate_opts(pi, values_t=True) on a finite-horizon handle first")
+        return vt
+
+    def evaluate_opts_device(self, pi_ptr: int | None = None, T: int = 1, values_t_ptr: int | None = None) -> int:
+        """evaluate_opts() with the policy (T*B*S int8, T = 1 or the horizon) and optionally V_t (H*B*S of
+        the handle's dtype) in device memory, 16-byte aligned (mgdp_vi_evaluate_opts_device).  pi_ptr None:
+        the handle's own pi (T = 1) or pi_t (T = horizon, needs keep_policy_t) -- pi_t* right after solve()."""
+        T = int(T)
+        if T != 1 and not (self.horizon > 0 and T == self.horizon):
+            raise ValueError(f"policy rows T = {T}: 1 or the handle's horizon ({self.horizon})")
+        if values_t_ptr is not None and self.horizon == 0:
+            raise ValueError("values_t needs a finite horizon")
+        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
+        self._values_t = None
+        _lib.check(self.L.mgdp_vi_evaluate_opts_device(
+            self.h, None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)), T,
+            None if values_t_ptr is None else ctypes.c_void_p(int(values_t_ptr)),
+            ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)), "mgdp_vi_evaluate_opts_device")
+        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
+        return self.sweeps
+
+    def improve_opts(self) -> int:
+        """improve() on a plain or lava="nodeath" handle (mgdp_vi_improve_opts); refused on a finite horizon."""
+        n = ctypes.c_int64(0)
+        _lib.check(self.L.mgdp_vi_improve_opts(self.h, ctypes.byref(n)), "mgdp_vi_improve_opts")
+        return n.value
+
+    def policy_iteration_opts(self, pi0=None, max_iters: int = 1000) -> dict:
+        """policy_iteration() on a plain or lava="nodeath" handle (mgdp_vi_policy_iteration_opts); refused
+        on a finite horizon (its greedy step is the solve itself)."""
+        a = None if pi0 is None else self._check_policy(pi0)
+        if int(max_iters) <= 0:
+            raise ValueError("max_iters must be > 0")
+        it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
+        _lib.check(self.L.mgdp_vi_policy_iteration_opts(self.h, None if a is None else _lib.ptr(a), int(max_iters),
+                                                        ctypes.byref(it), ctypes.byref(tot), ctypes.byref(ch),
+                                                        ctypes.byref(dv)), "mgdp_vi_policy_iteration_opts")
+        self.dv = dv.value
+        self.converged = dv.value < self.tol
+        self.sweeps = int(self.grid_sweeps().max())
+        return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
+
     # sweeps / dv / converged of the last result: read from solve()'s outputs while they are current
     def _result_attr(self, i, name):
         live = self.__dict__.get("_live")
@@ -599,12 +684,19 @@ class ValueIteration:
         return self.B * self.S * n_actions(self.model)
 
 
+def _has_options(kwargs) -> bool:
+    return bool(kwargs.get("horizon", 0)) or kwargs.get("lava", "terminal") == "nodeath"
+
+
 def policy_evaluation(grids, pi, **kwargs) -> VIResult:
     """V^pi of one policy per grid ((B, S) int8, see ValueIteration.evaluate) on one GPU; kwargs as
     ValueIteration (gamma, tol, slip_p, dtype, ...).  The result's pi is the evaluated policy."""
     vi = ValueIteration(grids, **kwargs)
     try:
-        vi.evaluate(pi)
+        if _has_options(kwargs):  # horizon / NoDeath: DESIGN.md section 19 ((H, B, S) accepted with a horizon)
+            vi.evaluate_opts(pi)
+        else:
+            vi.evaluate(pi)
         return vi.result()
     finally:
         vi.close()
@@ -615,7 +707,7 @@ def policy_iteration(grids, pi0=None, max_iters: int = 1000, **kwargs) -> VIResu
     eval_sweeps and changed, and its sweeps is the last evaluation's count."""
     vi = ValueIteration(grids, **kwargs)
     try:
-        r = vi.policy_iteration(pi0, max_iters=max_iters)
+        r = (vi.policy_iteration_opts if _has_options(kwargs) else vi.policy_iteration)(pi0, max_iters=max_iters)
         out = vi.result()
         out.iters, out.eval_sweeps, out.changed = r["iters"], r["eval_sweeps"], r["changed"]
         return out

@@ -1,0 +1,238 @@
+"""Policy evaluation under NoDeath lava and finite horizons: facts of the numpy
+restatement (tests/policy_opts_ref.py) that the GPU tests build on.  No GPU.
+
+The restatement meets the oracle where the two must agree: evaluating orc_vi_ex's own pi_t reproduces
+its V bit for bit, and with gamma = 1 the V_0 of any policy at an env's start state is the return the
+host rollout (tests/rollout_ref.py, the oracle's step()) collects for that policy.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import minigrid_dynamicprogramming_amd as mg
+from minigrid_dynamicprogramming_amd import _lib
+from minigrid_dynamicprogramming_amd.core import OBJECT_TO_IDX
+from oracle import oracle
+from tests import rollout_ref as rr
+from tests.policy_opts_ref import PolicyOptsRef, lava_entries, nodeath_table
+
+LAVA = OBJECT_TO_IDX["lava"]
+NEW_SYMBOLS = ("mgdp_vi_evaluate_opts", "mgdp_vi_evaluate_opts_device", "mgdp_vi_improve_opts",
+               "mgdp_vi_policy_iteration_opts")
+
+
+@functools.lru_cache(maxsize=None)
+def envs(env_id, B):
+    enc, agent, env = rr.grids(env_id, B)
+    return enc, agent, env, rr.cells_of(enc)
+
+
+def test_abi_exports_the_opts_entry_points():
+    L = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SIGNATURES and hasattr(L, name), name
+    assert L.mgdp_abi_version() == 12  # additive: the version does not move
+    assert L.mgdp_vi_evaluate_opts(None, None, 1, None, None, None, None) == _lib.MGDP_E_INVALID
+    assert L.mgdp_vi_evaluate_opts_device(None, None, 1, None, None, None, None) == _lib.MGDP_E_INVALID
+    assert L.mgdp_vi_improve_opts(None, None) == _lib.MGDP_E_INVALID
+    assert L.mgdp_vi_policy_iteration_opts(None, None, 1, None, None, None, None) == _lib.MGDP_E_INVALID
+    for m in ("evaluate_opts", "evaluate_opts_device", "values_t", "improve_opts", "policy_iteration_opts"):
+        assert callable(getattr(mg.ValueIteration, m))
+
+
+def test_nodeath_table_is_the_oracles():
+    """The lava cells are states, entering lava is R = death_cost and not terminal, the goal still is."""
+    _, _, _, cells = envs("MiniGrid-LavaGapS5-v0", 1)
+    nxt, rew, done = nodeath_table(cells[0], -0.25)
+    plain = oracle.build_table(0, cells[0])
+    on_lava = np.repeat(cells[0].reshape(-1) == LAVA, 4)
+    assert (nxt[on_lava, 0] >= 0).all() and (plain[0][on_lava, 0] < 0).all()
+    into = (rew == -0.25)
+    assert into.any() and not done[into].any() and (into.sum(axis=1) <= 1).all() and not into[:, [0, 1, 3, 4, 5, 6]].any()
+    assert (cells[0].reshape(-1)[nxt[into] >> 2] == LAVA).all()
+    assert ((rew == 1.0) == (done == 1)).all()
+
+
+XYD_SETS = (("MiniGrid-LavaCrossingS9N2-v0", 6), ("MiniGrid-Empty-6x6-v0", 2), ("MiniGrid-LavaGapS6-v0", 4))
+
+
+@pytest.mark.parametrize("gamma", [1.0, 0.95])
+@pytest.mark.parametrize("nodeath", [False, True])
+@pytest.mark.parametrize("slip", [None, 0.9])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("env_id,B", XYD_SETS)
+def test_xyd_evaluating_the_oracles_pi_t_reproduces_its_v(env_id, B, dtype, slip, nodeath, gamma):
+    H = 40
+    cells = envs(env_id, B)[3]
+    kw = dict(gamma=gamma, slip_p=slip, dtype=dtype)
+    o = oracle.value_iteration_ex(0, cells, lava_mode=int(nodeath), death_cost=-0.25, horizon=H, keep_policy_t=True, **kw)
+    ref = PolicyOptsRef(0, cells, lava="nodeath" if nodeath else "terminal", death_cost=-0.25, horizon=H, **kw)
+    r = ref.evaluate_horizon(o["pi_t"])
+    np.testing.assert_array_equal(r["V"], o["V"])
+    np.testing.assert_array_equal(r["pi"], o["pi"])
+    assert r["sweeps"] == o["sweeps"] == H and r["dv"] == o["dv"]
+    np.testing.assert_array_equal(r["Vt"][0], r["V"])
+
+
+@pytest.mark.parametrize("gamma", [1.0, 0.9])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("env_id,B,H", [("MiniGrid-DoorKey-5x5-v0", 4, 30), ("MiniGrid-DoorKey-6x6-v0", 3, 50)])
+def test_doorkey_evaluating_the_oracles_pi_t_reproduces_its_v(env_id, B, H, dtype, gamma):
+    cells = envs(env_id, B)[3]
+    o = oracle.value_iteration_ex(1, cells, gamma=gamma, dtype=dtype, horizon=H, keep_policy_t=True)
+    r = PolicyOptsRef(1, cells, gamma=gamma, dtype=dtype, horizon=H).evaluate_horizon(o["pi_t"])
+    np.testing.assert_array_equal(r["V"], o["V"])
+    np.testing.assert_array_equal(r["pi"], o["pi"])
+    assert r["dv"] == o["dv"]
+
+
+# ------------------------------------------------------------------------------------------------
+# The env tie on the host: gamma = 1, fp64, no slip -- V_0[b][start_b] is the return of the rollout.
+# ------------------------------------------------------------------------------------------------
+def tie_policies(pi_t, model, H):
+    """name -> policy: pi_t*, a time-indexed noisy one, a stationary noisy one, always forward, and pi_t*
+    with every third row forced to forward."""
+    third = pi_t.copy()
+    third[::3][third[::3] >= 0] = 2
+    return {"pi_t*": pi_t, "noisy_t": rr.noisy_policy(pi_t[0], model, 0.3, T=H),
+            "noisy": rr.noisy_policy(pi_t[0], model, 0.3), "forward": np.where(pi_t[0] >= 0, 2, -1).astype(np.int8),
+            "third_forward": third}
+
+
+def check_tie(model, env_id, B, H, lava="terminal", death_cost=-1.0):
+    enc, agent, env, cells = envs(env_id, B)
+    W = enc.shape[1]
+    m_id = 0 if model == "xyd" else 1
+    nd = lava == "nodeath"
+    o = oracle.value_iteration_ex(m_id, cells, gamma=1.0, dtype="f64", lava_mode=int(nd), death_cost=death_cost,
+                                  horizon=H, keep_policy_t=True)
+    ref = PolicyOptsRef(m_id, cells, gamma=1.0, dtype="f64", lava=lava, death_cost=death_cost, horizon=H)
+    start = rr.start_states(enc, agent, model)
+    entered = {}
+    for name, pol in tie_policies(o["pi_t"], model, H).items():
+        r = ref.evaluate_horizon(pol)
+        ro = rr.rollout_ref(enc, agent, pol, model, H, env.see_through_walls, trace_len=H,
+                            nd_types=("lava",) if nd else (), death_cost=death_cost)
+        assert (ro["status"] == 0).all()
+        v0 = r["V"][np.arange(B), start]
+        m = lava_entries(ro, cells, W) if nd else np.zeros(B, np.int64)
+        entered[name] = m
+        exact = m == 0  # at most one non-zero reward collected: terminal lava, DoorKey, no lava entered
+        np.testing.assert_array_equal(v0[exact], ro["ret"][exact], err_msg=name)
+        # m >= 1 entries: the same terms summed in opposite order, at most H additions a side, each
+        # within 2^-53 relative of a partial sum of magnitude <= H*|dc| + 1
+        bound = H * 2.0 ** -52 * (H * abs(death_cost) + 1.0)
+        assert (np.abs(v0 - ro["ret"])[~exact] <= bound).all(), name
+        if name == "noisy":  # a stationary noisy policy that truncates at H collects 0
+            assert (ro["truncated"] & (ro["ret"] == 0.0)).any()
+    return entered
+
+
+def test_env_tie_terminal_lava():
+    check_tie("xyd", "MiniGrid-LavaCrossingS9N2-v0", 4, 48)
+
+
+@pytest.mark.parametrize("env_id,H", [("MiniGrid-DoorKey-5x5-v0", 40), ("MiniGrid-DoorKey-6x6-v0", 60)])
+def test_env_tie_doorkey(env_id, H):
+    check_tie("doorkey", env_id, 3, H)
+
+
+def test_env_tie_nodeath_cheap_lava_is_walked_through():
+    m = check_tie("xyd", "MiniGrid-LavaCrossingS9N2-v0", 6, 48, "nodeath", -0.01)
+    assert (m["pi_t*"] >= 1).any() and m["pi_t*"].max() <= 2  # pi_t* itself crosses the lava
+
+
+def test_env_tie_nodeath_dear_lava_is_avoided_by_pi_star_only():
+    m = check_tie("xyd", "MiniGrid-LavaCrossingS9N2-v0", 6, 48, "nodeath", -0.3)
+    assert (m["pi_t*"] == 0).all() and (m["forward"] >= 1).any() and (m["third_forward"] >= 1).any()
+
+
+def test_env_tie_nodeath_unit_cost():
+    m = check_tie("xyd", "MiniGrid-LavaCrossingS9N2-v0", 4, 48, "nodeath", -1.0)
+    assert (m["pi_t*"] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------
+# NoDeath, horizon 0: discounted V^pi against orc_vi_ex(lava_mode = 1)
+# ------------------------------------------------------------------------------------------------
+ND_SETS = (("MiniGrid-LavaGapS5-v0", 3), ("MiniGrid-LavaGapS6-v0", 3), ("MiniGrid-LavaCrossingS9N1-v0", 3))
+BOUND = 2 * 1e-6 * 0.99 / (1 - 0.99)  # both loops stop with dV < tol under a gamma-contraction (section 13)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("env_id,B", ND_SETS)
+def test_nodeath_discounted_evaluation_of_pi_star(env_id, B, dtype):
+    cells = envs(env_id, B)[3]
+    o = oracle.value_iteration_ex(0, cells, dtype=dtype, lava_mode=1, death_cost=-1.0)
+    r = PolicyOptsRef(0, cells, dtype=dtype, lava="nodeath", death_cost=-1.0).evaluate(o["pi"])
+    print(env_id, dtype, "VI sweeps", o["sweeps"], "evaluation sweeps", r["sweeps"], "bit-equal",
+          np.array_equal(r["V"], o["V"]))
+    assert r["converged"] and np.abs(r["V"].astype(np.float64) - o["V"]).max() <= BOUND
+    np.testing.assert_array_equal(r["pi"], o["pi"])
+
+
+@pytest.mark.parametrize("env_id,B", ND_SETS)
+def test_nodeath_policy_iteration_from_all_forward(env_id, B):
+    cells = envs(env_id, B)[3]
+    o = oracle.value_iteration_ex(0, cells, dtype="f64", lava_mode=1, death_cost=-1.0)
+    ref = PolicyOptsRef(0, cells, dtype="f64", lava="nodeath", death_cost=-1.0)
+    first = ref.evaluate(np.full((B, ref.S), 2, np.int8))
+    assert first["V"].min() < 0  # forward into lava for ever: dc/(1-gamma) scale
+    r = ref.policy_iteration()
+    print(env_id, "policy iteration: iters", r["iters"], "changes", r["changes"], "first V.min", first["V"].min())
+    assert r["changed"] == 0 and np.abs(r["V"] - o["V"]).max() <= BOUND
+
+
+# ------------------------------------------------------------------------------------------------
+# The bad-lane rule and refusals
+# ------------------------------------------------------------------------------------------------
+def test_bad_lane_rule_names_lowest_grid_largest_t_lowest_state():
+    H = 6
+    cells = envs("MiniGrid-LavaGapS5-v0", 3)[3]
+    ref = PolicyOptsRef(0, cells, horizon=H)
+    pi = np.full((H, 3, ref.S), 2, np.int8)
+    v1 = np.nonzero(~ref.absorb[1])[0]
+    v2 = np.nonzero(~ref.absorb[2])[0]
+    pi[1, 1, v1[3]] = 7
+    pi[4, 1, v1[5]] = -1    # the larger t of the lower grid wins
+    pi[4, 1, v1[9]] = 9     # ... and in that row the lower state
+    pi[5, 2, v2[0]] = 7     # a higher grid, a larger t: not named
+    pi[:, 0, ref.absorb[0]] = 7  # absorbing states are ignored
+    with pytest.raises(ValueError, match=f"grid 1 t 4 state {v1[5]}: action -1 is outside \\[0, 7\\)"):
+        ref.evaluate_horizon(pi)
+    pi[4, 1, v1[5]] = 2
+    with pytest.raises(ValueError, match=f"grid 1 t 4 state {v1[9]}: action 9 "):
+        ref.evaluate_horizon(pi)
+    stat = np.full((3, ref.S), 2, np.int8)
+    stat[2, v2[4]] = 7
+    with pytest.raises(ValueError, match=f"grid 2 t 0 state {v2[4]}: action 7 "):
+        ref.evaluate_horizon(stat)
+
+
+def test_wrong_row_counts_are_refused():
+    cells = envs("MiniGrid-LavaGapS5-v0", 1)[3]
+    ref = PolicyOptsRef(0, cells, horizon=6)
+    for T in (2, 5, 7):
+        with pytest.raises(ValueError, match="T ="):
+            ref.evaluate_horizon(np.full((T, 1, ref.S), 2, np.int8))
+    with pytest.raises(ValueError, match="T ="):
+        PolicyOptsRef(0, cells, lava="nodeath").check_rows(np.full((6, 1, ref.S), 2, np.int8))
+
+
+def test_front_end_refuses_bad_shapes_and_dtypes_before_device_work():
+    vi = mg.ValueIteration.__new__(mg.ValueIteration)
+    vi.B, vi.S, vi.horizon = 2, 100, 6
+    assert vi._check_policy_opts(np.zeros((2, 100), np.int8))[1] == 1
+    assert vi._check_policy_opts(np.zeros((6, 2, 100), np.int64))[1] == 6
+    for shape in ((5, 2, 100), (2, 99), (1, 2, 100)):
+        with pytest.raises(ValueError, match="shape"):
+            vi._check_policy_opts(np.zeros(shape, np.int8))
+    with pytest.raises(ValueError, match="integer"):
+        vi._check_policy_opts(np.zeros((2, 100), np.float32))
+    with pytest.raises(ValueError, match="int8"):
+        vi._check_policy_opts(np.full((2, 100), 300, np.int32))
+    vi.horizon = 0
+    with pytest.raises(ValueError, match="shape"):
+        vi._check_policy_opts(np.zeros((6, 2, 100), np.int8))
+    vi.h = None  # nothing to destroy
