@@ -348,6 +348,19 @@ int mgdp_vi_kernel_time(mgdp_vi *vi, double *total_ms, int64_t *launches);
  * 0 launches: no server ran.  A diagnostic (the bench line reports it); no cost per solve. */
 int mgdp_vi_serve_clock(mgdp_vi *vi, double *sclk_mhz, double *server_us, int64_t *launches, double *solve_us,
                         int64_t *solves);
+/* The path the last served request of a lone deterministic XYD grid took on the pair server
+ * (variant "serve_pair"): 0 = swept (the pair loop, or the in-server fallback of a grid whose wave
+ * edges are open), 1 = the depth form (the solve read off every state's breadth-first depth from the
+ * goal plus one real sweep for V_K and pi_K; bit-identical K, dV, V and pi), 2 = the depth form
+ * abandoned at one of its limits and the request swept from V_0 inside the same request.
+ * counts (3 x int64, may be NULL): the handle's served requests by path, over the servers that have
+ * left.  The server keeps these words in registers and writes them with its exit words, so a request
+ * pays nothing for them and the call asks a resident server to leave first (as mgdp_vi_synchronize
+ * does); other servers report 0.
+ * Two run-time knobs (read at mgdp_vi_create): MGDP_SERVE_DEPTH (default 1; 0: every request sweeps)
+ * and MGDP_SERVE_DEPTH_MAX (the largest depth the form searches out before it hands the request to
+ * the pair loop; the default covers every grid the form accepts, a small value tests the hand-over). */
+int mgdp_vi_serve_path(mgdp_vi *vi, int32_t *path, int64_t *counts);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Batched env stepping: the gymnasium Env reset()/step() surface (minigrid_env.py:119-157,         */

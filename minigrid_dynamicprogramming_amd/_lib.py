@@ -118,6 +118,7 @@ SIGNATURES = {
     "mgdp_vi_enable_timing": (ctypes.c_int, [_P, _I32]),
     "mgdp_vi_kernel_time": (ctypes.c_int, [_P, _DP, _I64P]),
     "mgdp_vi_serve_clock": (ctypes.c_int, [_P, _DP, _DP, _I64P, _DP, _I64P]),
+    "mgdp_vi_serve_path": (ctypes.c_int, [_P, _I32P, _I64P]),
     "mgdp_vi_persistent": (ctypes.c_int, [_P, _I32P]),
     "mgdp_vi_kernel_name": (ctypes.c_char_p, [_P]),
     "mgdp_vi_variant": (ctypes.c_char_p, [_P]),

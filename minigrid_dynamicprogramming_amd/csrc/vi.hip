@@ -141,7 +141,8 @@ struct mgdp_vi {
     unsigned long long clk_tag = 0;  // the last server launch whose clock words were added
     double clk_cycles = 0.0, clk_ticks = 0.0, clk_busy = 0.0, clk_solves = 0.0;
     long long clk_launches = 0;
-    unsigned long long *d_gk = nullptr;    // the in-launch reduction's device words (GkCtx; plan.gk)
+    long long path_counts[3] = {0, 0, 0};  // served requests of the departed pair servers by path (mgdp_vi_serve_path)
+    unsigned long long *d_gk = nullptr;   // the in-launch reduction's device words (GkCtx; plan.gk)
     unsigned long long *d_breq = nullptr;  // the resident batch server's device words (kBreqWords): forwarded request, exit counter
     bool solving = false;                // inside mgdp_vi_solve: its run_local may use the batch server
     // policy evaluation / improvement (vi_eval.h): {policy error word, changed-state count}, allocated
@@ -445,7 +446,8 @@ int launch_serve_t(mgdp_vi *vi, unsigned int served) {
         hipExtLaunchKernelGGL(kern, dim3(1), dim3(p.block), p.serve_lds, vi->stream, tp.a, tp.b, 0, g,
                               make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv,
                               vi->d_hout, vi->d_hout + kHoutReq, (unsigned long long)served, vi->serve_idle_ticks,
-                              vi->serve_life_ticks, vi->kn.serve_pollers, vi->serve_tag, vi->kn.serve_poll_dma);
+                              vi->serve_life_ticks, vi->kn.serve_pollers, vi->serve_tag, vi->kn.serve_poll_dma,
+                              vi->kn.serve_depth ? vi->kn.serve_depth_max : 0);
     }
     MGDP_HIP(hipGetLastError());
     return 0;
@@ -615,6 +617,17 @@ int reduce_env(mgdp_vi *vi, int32_t *kmax, double *dvmax) {
             seg[5] += (double)(s[5] - s[0]);
             seg[6] += (double)(h[15] - s[5]);
         }
+        // the depth form (vi_serve_depth.h) stamps s[0] search start and s[5] search end (the columns "seen->first
+        // pair", "loop" and "left->publish" then read seen -> search start, search, search end -> publish) and,
+        // behind the publish, word 10: its V and pi stores issued.  That word is the previous solve's by now.
+        static double stored = 0;
+        static unsigned long long prev15 = 0;
+        if (prev15 && h[10] > prev15 && h[10] < h[14]) stored += (double)(h[10] - prev15);
+        prev15 = h[15];
+        if ((long long)n % 1000 == 0) {
+            std::fprintf(stderr, "serve trace depth: cycles per solve: publish -> V and pi stores issued %.1f\n", stored / 1000.0);
+            stored = 0;
+        }
         if ((long long)n % 1000 == 0) {
             std::fprintf(stderr, "serve trace pair: cycles per solve: seen->first pair %.1f, steady pair %.1f = reads %.1f + valu %.1f + "
                                  "flags/barrier %.1f, loop %.1f, left->publish %.1f, seen->publish %.1f\n",
@@ -677,6 +690,11 @@ void account_server_clock(mgdp_vi *vi) {
     vi->clk_ticks += (double)h[kHoutClk + 1];
     vi->clk_busy += (double)h[kHoutClk + 2];
     vi->clk_solves += (double)h[kHoutClk + 3];
+    // the departed launch's requests by path (Loop::serve_pair writes them; other servers leave them 0)
+    for (int i = 0; i < 3; ++i) {
+        vi->path_counts[i] += (long long)h[kHoutPath + 1 + i];
+        vi->h_out[kHoutPath + 1 + i] = 0;
+    }
     ++vi->clk_launches;
     vi->clk_tag = vi->serve_tag;
 }
@@ -747,6 +765,11 @@ int serve_request(mgdp_vi *vi) {
     }
     post_request(vi);
     if (!vi->serving) {
+        // A server that left after its last request (mgdp_vi_solve_last) may still be storing V / pi and its
+        // exit words: the new launch queues behind it on the stream in any case, and its clock and path words
+        // are counted only once its exit word is seen (a depth-form solve publishes well ahead of them).
+        if (vi->exiting)
+            if (int rc = wait_server_exit(vi)) return rc;
         vi->exiting = false;  // a departing earlier server is no longer the stream's last work
         if (int rc = launch_serve(vi, vi->epoch - 1u)) return rc;
         vi->serving = true;
@@ -906,7 +929,8 @@ int mgdp_vi_create(const mgdp_vi_desc *desc, mgdp_vi **out) {
         };
         big(vi->k.own, p.lds);
         big(vi->k.to, p.lds);
-        if (p.serve_shape) big(vi->k.serve, p.serve_lds);
+        // (the pair server also holds the depth form's static level masks and table: vi_serve_depth.h)
+        if (p.serve_shape) big(vi->k.serve, p.serve_lds + (p.serve_kern == Loop::serve_pair ? kDepthStaticLds : 0));
         if (ea != hipSuccess) {
             delete vi;
             return hip_fail(ea, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", __FILE__, __LINE__);
@@ -2090,6 +2114,18 @@ int mgdp_vi_serve_clock(mgdp_vi *vi, double *sclk_mhz, double *server_us, int64_
     if (launches) *launches = vi->clk_launches;
     if (solve_us) *solve_us = vi->clk_solves > 0 ? vi->clk_busy * 0.01 / vi->clk_solves : 0.0;
     if (solves) *solves = (int64_t)vi->clk_solves;
+    return 0;
+}
+
+int mgdp_vi_serve_path(mgdp_vi *vi, int32_t *path, int64_t *counts) {
+    MGDP_CHECK(vi && path, MGDP_E_INVALID, "null argument");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;  // the server writes the words behind its publish: it has left now
+    MGDP_HIP(hipStreamSynchronize(vi->stream));
+    account_server_clock(vi);
+    *path = (int32_t)vi->h_out[kHoutPath];
+    if (counts)
+        for (int i = 0; i < 3; ++i) counts[i] = (int64_t)vi->path_counts[i];
     return 0;
 }
 

@@ -127,6 +127,12 @@ struct ServeCtx {
     ServePairTopo<T> sp;                   // Loop::serve_pair: its own per-grid constants
     int ew;  // Loop::serve_ew / serve_pair: 0 = the grid falls back, 1 = the served loop, 2 = the same, first
              // solve of the grid (tiles to clear)
+    // Loop::serve_pair, the depth form (vi_serve_depth.h): the grid's masks, the launch's two constants
+    // (depth_max 0: MGDP_SERVE_DEPTH=0, every request sweeps) and the path the last request took
+    // (mgdp_vi_serve_path: 0 swept, 1 depth form, 2 depth form abandoned, then swept)
+    ServeDepthTopo depth;
+    int depth_max, depth_ktol;
+    mutable int path;
 };
 
 // One grid of a fused launch or of a served request, for every Loop family: prologue (resume, learned
@@ -285,9 +291,18 @@ __device__ __forceinline__ bool fused_grid(const Geo &geo, const Coef<T> &cf, co
             static_assert(SERVED && MODEL == MGDP_MODEL_XYD && !SLIP && MAP == MGDP_MAP_CELL, "served plain XYD grid");
             if (sc->ew != 0) {
                 if constexpr (L == Loop::serve_pair) {
-                    const int te = serve_pair_tile_elems(geo.HWs, geo.W);  // a tile: [pad][HWs][pad] cells of 4 planes
-                    fused_serve_pair<T>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, sc->topo, sc->sp,
-                                        sc->ew == 2);
+                    // a fresh request of a grid the depth form takes: read off the goal depth; past the form's
+                    // limits (path 2) nothing has been published or stored and the request sweeps from V_0
+                    int path = 0;
+                    if (sc->depth.ok && k == 0)
+                        path = fused_serve_depth<T>(geo, cf, V + vb, pi + vb, k, dvl, done, sc->topo, sc->depth, sc->depth_max,
+                                                    sc->depth_ktol);
+                    sc->path = path;
+                    if (path != 1) {
+                        const int te = serve_pair_tile_elems(geo.HWs, geo.W);  // a tile: [pad][HWs][pad] cells of 4 planes
+                        fused_serve_pair<T>(geo, cf, V0, V0 + te, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, sc->topo,
+                                            sc->sp, sc->ew == 2);
+                    }
                 } else {
                     fused_serve_xyd<T>(geo, cf, V0, V1, slots, flags, V + vb, V + vb, pi + vb, k, dvl, done, sc->topo, sc->ew == 2);
                 }
@@ -429,6 +444,7 @@ vi_fused_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__res
 // (s_memrealtime, 100 MHz); the host relaunches the server if a request finds it gone.
 constexpr int kHoutWords = 32;  // host-mapped words of a handle (mgdp_vi::h_out)
 constexpr int kHoutReq = 16;    // request word; its source word follows (one 16-B pair)
+constexpr int kHoutPath = 28;   // Loop::serve_pair: the last request's path, then this launch's requests by path [3]
 constexpr int kHoutClk = 24;    // a departing server's {shader-clock cycles, 100 MHz ticks} of its life,
                                 // then {100 MHz ticks inside its solves, solves served}
 constexpr unsigned long long kServeQuit = ~0ull;
@@ -464,7 +480,7 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
                 int8_t *__restrict__ pi, int32_t *__restrict__ kenv, double *__restrict__ dvenv,
                 unsigned long long *__restrict__ host_out, const unsigned long long *__restrict__ host_cmd,
                 unsigned long long served, unsigned long long idle_ticks, unsigned long long life_ticks, int pollers,
-                unsigned long long exit_tag, int poll_dma) {
+                unsigned long long exit_tag, int poll_dma, int depth_max) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long s_cmd, s_src;
     __shared__ __attribute__((aligned(16))) unsigned long long s_box[2];  // poll mailbox: {request, source}
@@ -483,9 +499,18 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
     // GPU-side time of the solves (thread 0: the poll that saw the request -> the solve's end,
     // s_memrealtime ticks already read for the idle limit, so no extra counter read per solve)
     unsigned long long t_seen = t_start, busy = 0, solves = 0;
+    // the depth form's table of this launch (gamma, tol and the dtype are the handle's): vi_serve_depth.h
+    if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD)
+        if (depth_max > 0) serve_depth_table<T>(cf);
     __syncthreads();
     // the grid stays put between kServeNewCells requests: resolve this thread's cell topology once
     ServeCtx<T, MODEL> sc = {};
+    unsigned long long n_path[3] = {0, 0, 0};  // thread 0: this launch's requests by path (Loop::serve_pair)
+    int last_path = 0;
+    if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) {
+        sc.depth_max = depth_max;
+        sc.depth_ktol = depth_max > 0 ? serve_depth_ktol() : 0;
+    }
     __shared__ int s_ew;
     auto resolve = [&]() {
         if constexpr (L == Loop::generic || loop_is_serve_ew(L)) {
@@ -495,6 +520,8 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
         }
         if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD) sc.sp = serve_pair_topo<T>(cl, geo, cf, sc.topo, (int)threadIdx.x);
         if constexpr (loop_is_serve_ew(L)) sc.ew = serve_ew_ok(cl, geo, &s_ew) ? 2 : 0;
+        if constexpr (L == Loop::serve_pair && MODEL == MGDP_MODEL_XYD)
+            sc.depth = serve_depth_topo(cl, geo, depth_max > 0 && sc.ew != 0);
     };
     resolve();
     while (true) {
@@ -556,11 +583,29 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
         }
         int k;
         double dvl;
+        sc.path = 0;
         if (!fused_grid<T, MODEL, SLIP, MAP, true, L, N>(geo, cf, cells, V, pi, kenv, dvenv, host_out, -1, 1, true,
                                                    (unsigned int)cmd, 0, k, dvl, nullptr, &sc) &&
             threadIdx.x == 0)
             publish_tagged(host_out, k, dvl, (unsigned int)cmd);
-        if (sc.ew == 2) sc.ew = 1;  // the tiles' pads stay +0 until the next grid
+        if constexpr (L == Loop::serve_pair) {
+            // the path this request took, counted in registers: the words leave with the server's exit words
+            // (mgdp_vi_serve_path reads them once it has left), so a request pays no host store for them
+            if (threadIdx.x == 0) {
+                last_path = sc.path;
+                if (sc.path == 0) ++n_path[0];  // (no indexed access: the counters stay in registers)
+                else if (sc.path == 1) ++n_path[1];
+                else ++n_path[2];
+#ifdef MGDP_SERVE_TRACE
+                if (sc.path == 1)  // the depth form's "V and pi stores issued" stamp (vi_serve_depth.h)
+                    __hip_atomic_store(host_out + 10, g_pair_trace[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+            }
+            // a depth-form solve leaves the tiles alone: their once-per-grid clear is still to come
+            if (sc.ew == 2 && sc.path != 1) sc.ew = 1;  // the tiles' pads stay +0 until the next grid
+        } else if (sc.ew == 2) {
+            sc.ew = 1;
+        }
         served = cmd;
         t_last = __builtin_amdgcn_s_memrealtime();
         if (threadIdx.x == 0) {
@@ -588,6 +633,13 @@ vi_serve_kernel(Geo geo, Coef<T> cf, uint8_t *__restrict__ cells, T *__restrict_
                            __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(host_out + kHoutClk + 2, busy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(host_out + kHoutClk + 3, solves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if constexpr (L == Loop::serve_pair) {
+            if (solves > 0) {  // the last request's path and this launch's requests by path
+                __hip_atomic_store(host_out + kHoutPath, (unsigned long long)last_path, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                for (int i = 0; i < 3; ++i)
+                    __hip_atomic_store(host_out + kHoutPath + 1 + i, n_path[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
         __hip_atomic_store(host_out + 11, exit_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }

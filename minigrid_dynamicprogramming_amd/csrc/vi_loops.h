@@ -890,6 +890,12 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     }
 }
 
+}  // namespace mgdp
+// The depth form of the same served grids (fused_serve_depth): a fresh request read off the goal depth
+// instead of swept; it hands the request to fused_serve_pair where its limits end.
+#include "vi_serve_depth.h"
+namespace mgdp {
+
 // Batched XYD grids with N cells per thread (cells t + j*blockDim, j < N; HWs = N * blockDim): the
 // same sweep as fused_fast_xyd_soa on 1/N of the waves, so the per-sweep fixed work of a wave (flag
 // read, address set-up, ballot, barrier) is paid once per N cells.  Plain deterministic / slip

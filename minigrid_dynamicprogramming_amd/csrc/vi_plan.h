@@ -73,6 +73,8 @@ struct ViKnobs {
     int serve_ew = 1;    // MGDP_SERVE_EW: served lone plain XYD grid on fused_serve_xyd
     int serve_pair = 1;  // MGDP_SERVE_PAIR: ... two sweeps per barrier (fused_serve_pair)
     int serve_band = 0;  // MGDP_SERVE_BAND: ... on one wave in column bands (A/B)
+    int serve_depth = 1;  // MGDP_SERVE_DEPTH: the pair server reads a fresh request off the goal depth (fused_serve_depth); 0: every request sweeps
+    int serve_depth_max = 1 << 20;  // MGDP_SERVE_DEPTH_MAX: the largest depth the form searches out before it hands the request to the pair loop
     int dk_1t = 0;       // MGDP_DK_1T: batched fp32 DoorKey on one LDS tile
     int dk_half = -1;    // MGDP_DK_HALF: -1 = fp64 and lone grids (DoorKey-16 x 65536 fp64 9.9e12 vs 2.8e12 updates/s, fp32 1.90e13 vs 2.22e13; profiles/r02_dk_half/)
     int dk_rows = 1;     // MGDP_DK_ROWS: width-16 DoorKey on whole-row maps (0: fused_fast_dk_soa, half its LDS cycles on bank conflicts)
@@ -127,6 +129,8 @@ inline const KnobSpec *knob_table(int *n) {
         {"MGDP_SERVE_EW", &K::serve_ew, nullptr, nullptr, T::integer, 0, 0},
         {"MGDP_SERVE_PAIR", &K::serve_pair, nullptr, nullptr, T::integer, 0, 0},
         {"MGDP_SERVE_BAND", &K::serve_band, nullptr, nullptr, T::integer, 0, 0},
+        {"MGDP_SERVE_DEPTH", &K::serve_depth, nullptr, nullptr, T::flag, 0, 0},
+        {"MGDP_SERVE_DEPTH_MAX", &K::serve_depth_max, nullptr, nullptr, T::at_least, 1, 0},
         {"MGDP_DK_1T", &K::dk_1t, nullptr, nullptr, T::flag, 0, 0},
         {"MGDP_DK_HALF", &K::dk_half, nullptr, nullptr, T::flag, 0, 0},
         {"MGDP_DK_ROWS", &K::dk_rows, nullptr, nullptr, T::flag, 0, 0},

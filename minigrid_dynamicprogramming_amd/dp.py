@@ -673,6 +673,21 @@ class ValueIteration:
         return {"sclk_mhz": mhz.value, "server_us": us.value, "launches": n.value, "gpu_solve_us": sus.value,
                 "solves": ns.value}
 
+    def _serve_path(self):
+        path, counts = ctypes.c_int32(-1), (ctypes.c_int64 * 3)()
+        _lib.check(self.L.mgdp_vi_serve_path(self.h, ctypes.byref(path), counts), "mgdp_vi_serve_path")
+        return path.value, tuple(int(x) for x in counts)
+
+    def serve_path(self) -> int:
+        """The path the last served request took on the pair server (mgdp_vi_serve_path): 0 swept, 1 the
+        depth form, 2 the depth form abandoned at a limit, then swept.  Asks a resident server to leave."""
+        return self._serve_path()[0]
+
+    def serve_path_counts(self) -> tuple[int, int, int]:
+        """The handle's served requests by path (0, 1, 2), over the servers that have left; asks a resident
+        server to leave, as serve_path() does."""
+        return self._serve_path()[1]
+
     def kernel_time(self) -> tuple[float, int]:
         ms = ctypes.c_double(0)
         n = ctypes.c_int64(0)
