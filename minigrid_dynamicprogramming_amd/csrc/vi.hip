@@ -25,9 +25,10 @@
 //                     LDS tile of the neighbourhood), updated from LDS, written back.
 //   vi_eval_kernel / vi_improve_kernel (vi_eval.h)  policy evaluation under the same protocol, and the
 //                     greedy improvement step.
-//   vi_eval_fh_kernel / vi_eval_nd_kernel / vi_improve_nd_kernel (vi_eval_opts.h)  the same under the
-//                     handle options: finite-horizon backward induction of a stationary or time-indexed
-//                     policy, and evaluation / improvement on NoDeath lava.
+//   vi_eval_fh_kernel / vi_eval_nd_kernel (vi_eval_opts.h)  the same under the handle options:
+//                     finite-horizon backward induction of a stationary or time-indexed policy, and
+//                     evaluation on NoDeath lava (the improvement there is vi_improve_kernel's ND
+//                     form).
 // Device code is split into vi_model.h (model), vi_loops.h (workgroup loops), vi_kernels.h
 // (kernels); this file holds the host side and the C ABI.  Which loop a handle runs is decided once,
 // in vi_plan.h (host-plain: plan_vi); vi_layout.h holds the LDS sizes host and device share.
@@ -1570,20 +1571,48 @@ int mgdp_vi_resume(mgdp_vi *vi, const void *V, int32_t k, double dv, int32_t *sw
     return 0;
 }
 
-// Policy evaluation, improvement and policy iteration (kernels in vi_eval.h).
+// Policy evaluation, improvement and policy iteration (DESIGN.md sections 13 and 19; kernels in vi_eval.h and
+// vi_eval_opts.h).  One implementation per operation, over (pi, T rows, V_t): the plain ABI names are its
+// strict form (no option handle, T = 1, no V_t), the *_opts names check T / V_t and take any handle.
 // An evaluation is the solve's protocol on vi_eval_kernel: every grid to its own stop, the grids that
-// stopped with dV != 0 to K = max k_e, then the global rule sweep by sweep if dV(K) >= tol.
+// stopped with dV != 0 to K = max k_e, then the global rule sweep by sweep if dV(K) >= tol; on a finite
+// horizon it is one launch of exactly H sweeps.
 extern "C++" {  // the launch helpers are templates
 namespace {
-int eval_supported(const mgdp_vi *vi, const char *what) {
+inline bool option_handle(const mgdp_vi *vi) { return vi->d.horizon > 0 || vi->d.lava_mode != MGDP_LAVA_TERMINAL; }
+
+// `opts`: the call came through an *_opts name.  The plain names refuse an option handle; the limits of the
+// option kernels (one thread per cell, the finite-horizon error word) bind an option handle only -- a plain
+// handle above 1024 cells takes vi_eval_kernel's strided form through either name.
+int eval_supported(const mgdp_vi *vi, const char *what, bool opts) {
     MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
     MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED, MGDP_E_UNSUPPORTED, "%s runs on the fused method only", what);
-    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED, "%s is defined for the discounted problem (horizon 0)", what);
-    MGDP_CHECK(vi->d.lava_mode == MGDP_LAVA_TERMINAL, MGDP_E_UNSUPPORTED,
-               "%s needs terminal lava (NoDeath makes V negative)", what);
+    if (!opts) {
+        MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED, "%s is defined for the discounted problem (horizon 0)", what);
+        MGDP_CHECK(vi->d.lava_mode == MGDP_LAVA_TERMINAL, MGDP_E_UNSUPPORTED,
+                   "%s needs terminal lava (NoDeath makes V negative)", what);
+    }
+    const bool oh = option_handle(vi);
+    MGDP_CHECK(!oh || vi->HW <= 1024, MGDP_E_UNSUPPORTED, "%s under horizon / lava options needs W*H <= 1024", what);
     const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
     MGDP_CHECK(s.lds <= 160 * 1024, MGDP_E_UNSUPPORTED,
                "%s: grid too large for the LDS-resident evaluation (%d B > 160 KiB)", what, s.lds);
+    MGDP_CHECK(!oh || (vi->d.horizon <= kFhMaxH && vi->d.B <= kFhMaxB), MGDP_E_UNSUPPORTED,
+               "%s: horizon %d / batch %d exceed the policy error word", what, vi->d.horizon, vi->d.B);
+    return 0;
+}
+// improvement and policy iteration: an *_opts name refuses a finite horizon in its own words, first
+int greedy_supported(const mgdp_vi *vi, const char *what, bool opts) {
+    MGDP_CHECK(!opts || vi->d.horizon == 0, MGDP_E_UNSUPPORTED,
+               "%s is refused on a finite horizon: its greedy step is the solve itself", what);
+    return eval_supported(vi, what, opts);
+}
+// the policy rows T and V_t of an *_opts name (the plain names: T = 1, no V_t)
+int eval_rows_supported(const mgdp_vi *vi, int32_t T, const void *V_t) {
+    const int H = vi->d.horizon;
+    MGDP_CHECK(T == 1 || (H > 0 && T == H), MGDP_E_INVALID,
+               "policy rows T = %d: 1 (stationary)%s", T, H > 0 ? " or the handle's horizon" : " on a horizon-0 handle");
+    MGDP_CHECK(!(V_t && H == 0), MGDP_E_INVALID, "V_t needs a finite horizon");
     return 0;
 }
 
@@ -1603,16 +1632,17 @@ int eval_buffers(mgdp_vi *vi) {
     return 0;
 }
 
-template <typename T, int MODEL, bool SLIP>
-int launch_eval_t(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+// The launch of an evaluation kernel (vi_eval_kernel, vi_eval_nd_kernel, vi_eval_fh_kernel): the arguments
+// the three share, the kernel's own (`tail`), then in_kernel_reduce and the epoch.
+template <typename T, typename K, typename... Tail>
+int launch_eval_kernel(mgdp_vi *vi, K kern, const int8_t *pi_src, Tail... tail) {
     const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    auto kern = vi_eval_kernel<T, MODEL, SLIP>;
     if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
     TimedPair tp;
     if (int rc = timed_begin(vi, -1, &tp)) return rc;
     hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
                           make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
-                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, k_target, vi->fresh,
+                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, tail...,
                           vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
     MGDP_HIP(hipGetLastError());
     vi->fresh = 0;
@@ -1623,77 +1653,61 @@ int launch_eval_t(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
     return 0;
 }
 
-template <typename T, int MODEL, bool SLIP>
-int launch_improve_t(mgdp_vi *vi) {
-    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    auto kern = vi_improve_kernel<T, MODEL, SLIP>;
-    if (s.improve_lds > 64 * 1024)
-        MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.improve_lds));
-    hipLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.improve_block), s.improve_lds, vi->stream, eval_geo(vi, s),
-                       make_coef<T>(vi), vi->d_cells, (const T *)vi->d_V[0], vi->d_pi, vi->d_eval + 1);
-    MGDP_HIP(hipGetLastError());
-    return 0;
+// Dispatch on (dtype, model, slip, NoDeath lava); the mapping does not apply (one thread per cell).  DoorKey
+// has neither slip nor NoDeath (mgdp_vi_create), so neither is instantiated.
+template <typename T, template <typename, int, bool, bool> class F, typename... Args>
+int dispatch_eval_t(mgdp_vi *vi, Args... args) {
+    if (vi->d.model == MGDP_MODEL_DOORKEY) return F<T, MGDP_MODEL_DOORKEY, false, false>::run(vi, args...);
+    const bool nd = vi->d.lava_mode == MGDP_LAVA_NODEATH;
+    if (vi->d.slip_p >= 0.0) return nd ? F<T, MGDP_MODEL_XYD, true, true>::run(vi, args...) : F<T, MGDP_MODEL_XYD, true, false>::run(vi, args...);
+    return nd ? F<T, MGDP_MODEL_XYD, false, true>::run(vi, args...) : F<T, MGDP_MODEL_XYD, false, false>::run(vi, args...);
+}
+template <template <typename, int, bool, bool> class F, typename... Args>
+int dispatch_eval(mgdp_vi *vi, Args... args) {
+    return vi->d.dtype == MGDP_F32 ? dispatch_eval_t<float, F>(vi, args...) : dispatch_eval_t<double, F>(vi, args...);
 }
 
-// dispatch on (dtype, model, slip); the mapping does not apply (one thread per cell)
-template <typename T>
-int launch_eval_m(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
-    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_eval_t<T, MGDP_MODEL_DOORKEY, false>(vi, k_target, pi_src);
-    return vi->d.slip_p >= 0.0 ? launch_eval_t<T, MGDP_MODEL_XYD, true>(vi, k_target, pi_src)
-                               : launch_eval_t<T, MGDP_MODEL_XYD, false>(vi, k_target, pi_src);
-}
-// NoDeath lava (reached through the *_opts entry points only): vi_eval_nd_kernel under the same protocol
-template <typename T, bool SLIP>
-int launch_eval_nd_t(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
-    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    auto kern = vi_eval_nd_kernel<T, SLIP>;
-    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
-    TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
-    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
-                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
-                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, k_target, vi->fresh,
-                          vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
-    MGDP_HIP(hipGetLastError());
-    vi->fresh = 0;
-    if (vi->d.B > vi->kn.inkernel_max) {
-        launch_reduce(vi, vi->d_hout);
-        MGDP_HIP(hipGetLastError());
+template <typename T, int MODEL, bool SLIP, bool ND>
+struct EvalF {  // NoDeath lava: vi_eval_nd_kernel under the same protocol
+    static int run(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
+        if constexpr (ND) return launch_eval_kernel<T>(vi, vi_eval_nd_kernel<T, SLIP>, pi_src, k_target, vi->fresh);
+        else return launch_eval_kernel<T>(vi, vi_eval_kernel<T, MODEL, SLIP>, pi_src, k_target, vi->fresh);
     }
-    return 0;
-}
-template <typename T>
-int launch_eval_nd(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
-    return vi->d.slip_p >= 0.0 ? launch_eval_nd_t<T, true>(vi, k_target, pi_src) : launch_eval_nd_t<T, false>(vi, k_target, pi_src);
-}
-template <typename T, bool SLIP>
-int launch_improve_nd_t(mgdp_vi *vi) {
-    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    hipLaunchKernelGGL((vi_improve_nd_kernel<T, SLIP>), dim3(vi->d.B), dim3(s.improve_block), s.improve_lds, vi->stream,
-                       eval_geo(vi, s), make_coef<T>(vi), vi->d_cells, (const T *)vi->d_V[0], vi->d_pi, vi->d_eval + 1);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-template <typename T>
-int launch_improve_nd(mgdp_vi *vi) {
-    return vi->d.slip_p >= 0.0 ? launch_improve_nd_t<T, true>(vi) : launch_improve_nd_t<T, false>(vi);
-}
+};
+template <typename T, int MODEL, bool SLIP, bool ND>
+struct EvalFhF {  // + (time-indexed policy, V_t stored)
+    template <bool TI, bool VT>
+    static int launch(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
+        return launch_eval_kernel<T>(vi, vi_eval_fh_kernel<T, MODEL, SLIP, ND, TI, VT>, pi_src, (const T *)vi->d_rgoal,
+                                     (T *)d_vt, vi->d.horizon);
+    }
+    static int run(mgdp_vi *vi, const int8_t *pi_src, bool ti, void *d_vt) {
+        const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+        constexpr int max_block = kEvalFhBlock<T, MODEL>;
+        MGDP_CHECK(s.block <= max_block, MGDP_E_UNSUPPORTED, "policy evaluation: %d cell slots exceed the kernel's %d threads",
+                   s.block, max_block);
+        if (ti) return d_vt ? launch<true, true>(vi, pi_src, d_vt) : launch<true, false>(vi, pi_src, d_vt);
+        return d_vt ? launch<false, true>(vi, pi_src, d_vt) : launch<false, false>(vi, pi_src, d_vt);
+    }
+};
+template <typename T, int MODEL, bool SLIP, bool ND>
+struct ImproveF {
+    static int run(mgdp_vi *vi) {
+        const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+        auto kern = vi_improve_kernel<T, MODEL, SLIP, ND>;
+        if (s.improve_lds > 64 * 1024)
+            MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.improve_lds));
+        hipLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.improve_block), s.improve_lds, vi->stream, eval_geo(vi, s),
+                           make_coef<T>(vi), vi->d_cells, (const T *)vi->d_V[0], vi->d_pi, vi->d_eval + 1);
+        MGDP_HIP(hipGetLastError());
+        return 0;
+    }
+};
 
-int launch_eval(mgdp_vi *vi, int k_target, const int8_t *pi_src) {
-    if (vi->d.lava_mode == MGDP_LAVA_NODEATH)
-        return vi->d.dtype == MGDP_F32 ? launch_eval_nd<float>(vi, k_target, pi_src) : launch_eval_nd<double>(vi, k_target, pi_src);
-    return vi->d.dtype == MGDP_F32 ? launch_eval_m<float>(vi, k_target, pi_src) : launch_eval_m<double>(vi, k_target, pi_src);
-}
-template <typename T>
-int launch_improve_m(mgdp_vi *vi) {
-    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_improve_t<T, MGDP_MODEL_DOORKEY, false>(vi);
-    return vi->d.slip_p >= 0.0 ? launch_improve_t<T, MGDP_MODEL_XYD, true>(vi) : launch_improve_t<T, MGDP_MODEL_XYD, false>(vi);
-}
-
-// The evaluation of the policy at d_src (device; the handle's own buffer included), stream idle of
-// servers.  The dispatch order a later solve would learn from the previous solve's executed sweeps is
-// learned first: the evaluation overwrites d_kexec with its own and must not feed that order.
-int eval_run(mgdp_vi *vi, const int8_t *d_src, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
+// Before an evaluation's first launch, stream idle of servers.  The dispatch order a later solve would learn
+// from the previous solve's executed sweeps is learned first: the evaluation overwrites d_kexec with its own
+// and must not feed that order.
+int eval_begin(mgdp_vi *vi) {
     if (!vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi))
         if (int rc = learn_dispatch(vi)) return rc;
     if (int rc = eval_buffers(vi)) return rc;
@@ -1704,45 +1718,84 @@ int eval_run(mgdp_vi *vi, const int8_t *d_src, int32_t *sweeps_out, double *dv_o
     vi->k_done_valid = false;
     vi->sweeps = vi->converged = 0;
     vi->evaluated = true;  // whatever follows, kenv / dvenv / V are no longer a solve's
-    int32_t k = 0, km = 0;
-    double dv = 0.0;
-    if (int rc = launch_eval(vi, -1, d_src)) return rc;
-    if (int rc = reduce_env(vi, &k, &dv)) return rc;
-    unsigned long long err = kEvalNoError;
-    MGDP_HIP(hipMemcpyAsync(&err, vi->d_eval, sizeof(err), hipMemcpyDeviceToHost, vi->stream));
+    return 0;
+}
+// the policy error word the first launch left (kEvalNoError: every entry in range); drains the stream
+int eval_error_word(mgdp_vi *vi, unsigned long long *err) {
+    *err = kEvalNoError;
+    MGDP_HIP(hipMemcpyAsync(err, vi->d_eval, sizeof(*err), hipMemcpyDeviceToHost, vi->stream));
     MGDP_HIP(hipStreamSynchronize(vi->stream));
     vi->k_done_valid = false;
+    return 0;
+}
+int eval_finish(mgdp_vi *vi, int32_t k, double dv, int32_t converged, int32_t *sweeps_out, double *dv_out,
+                int32_t *converged_out) {
+    vi->k_done = k;
+    vi->k_done_valid = false;  // the protocol entry points need a reset after an evaluation
+    vi->sweeps = k;
+    vi->converged = converged;
+    if (sweeps_out) *sweeps_out = k;
+    if (dv_out) *dv_out = dv;
+    if (converged_out) *converged_out = converged;
+    return 0;
+}
+
+// The discounted evaluation of the policy at d_src (device; the handle's own buffer included).
+int eval_run(mgdp_vi *vi, const int8_t *d_src, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
+    if (int rc = eval_begin(vi)) return rc;
+    int32_t k = 0, km = 0;
+    double dv = 0.0;
+    if (int rc = dispatch_eval<EvalF>(vi, -1, d_src)) return rc;
+    if (int rc = reduce_env(vi, &k, &dv)) return rc;
+    unsigned long long err;
+    if (int rc = eval_error_word(vi, &err)) return rc;
     MGDP_CHECK(err == kEvalNoError, MGDP_E_INVALID, "policy: grid %d state %d: action %d is outside [0, %d)",
                (int)(err >> 32), (int)((err >> 8) & 0xffffffu), (int)(int8_t)(err & 0xffu), vi->A);
     // run_to(K): nothing to launch when every grid is at K or at an exact fixed point (mgdp_vi_run_to)
     if (!(vi->k_min == k || (vi->dv_red == 0.0 && vi->k_min > 0))) {
-        if (int rc = launch_eval(vi, k, nullptr)) return rc;
+        if (int rc = dispatch_eval<EvalF>(vi, k, nullptr)) return rc;
         if (int rc = reduce_env(vi, &km, &dv)) return rc;
         MGDP_CHECK(km == k, MGDP_E_INVALID, "evaluate: run_to(%d) ended at sweep %d", k, km);
     }
     while (!(dv < vi->d.tol) && k < vi->d.max_sweeps) {  // contraction broken by rounding: global rule
-        if (int rc = launch_eval(vi, k + 1, nullptr)) return rc;
+        if (int rc = dispatch_eval<EvalF>(vi, k + 1, nullptr)) return rc;
         if (int rc = reduce_env(vi, &km, &dv)) return rc;
         ++k;
     }
-    vi->k_done = k;
-    vi->k_done_valid = false;  // the protocol entry points need a reset after an evaluation
-    vi->sweeps = k;
-    vi->converged = dv < vi->d.tol;
-    if (sweeps_out) *sweeps_out = k;
-    if (dv_out) *dv_out = dv;
-    if (converged_out) *converged_out = vi->converged;
-    return 0;
+    return eval_finish(vi, k, dv, dv < vi->d.tol, sweeps_out, dv_out, converged_out);
+}
+
+// The finite-horizon evaluation of the policy at d_src (T rows: 1 or H), one launch of exactly H sweeps.
+int eval_fh_run(mgdp_vi *vi, const int8_t *d_src, int T, void *d_vt, int32_t *sweeps_out, double *dv_out,
+                int32_t *converged_out) {
+    const int H = vi->d.horizon;
+    if (int rc = eval_begin(vi)) return rc;
+    int32_t k = 0;
+    double dv = 0.0;
+    if (int rc = dispatch_eval<EvalFhF>(vi, d_src, T != 1, d_vt)) return rc;
+    if (int rc = reduce_env(vi, &k, &dv)) return rc;
+    unsigned long long err;
+    if (int rc = eval_error_word(vi, &err)) return rc;
+    if (err != kEvalNoError) {
+        const int row = (int)((err >> kFhRowShift) & (unsigned long long)(kFhMaxH - 1));
+        MGDP_CHECK(false, MGDP_E_INVALID, "policy: grid %d t %d state %d: action %d is outside [0, %d)",
+                   (int)(err >> kFhGridShift), T == 1 ? 0 : H - 1 - row, (int)((err >> 8) & 0x3fffu),
+                   (int)(int8_t)(err & 0xffu), vi->A);
+    }
+    MGDP_CHECK(k == H && vi->k_min == H, MGDP_E_INVALID, "evaluate: the horizon's %d sweeps ended at %d..%d", H, vi->k_min, k);
+    return eval_finish(vi, k, dv, 1, sweeps_out, dv_out, converged_out);  // a finite horizon is exact after H sweeps
+}
+
+int eval_policy(mgdp_vi *vi, const int8_t *d_src, int T, void *d_vt, int32_t *sweeps_out, double *dv_out,
+                int32_t *converged_out) {
+    if (vi->d.horizon == 0) return eval_run(vi, d_src, sweeps_out, dv_out, converged_out);
+    return eval_fh_run(vi, d_src, T, d_vt, sweeps_out, dv_out, converged_out);
 }
 
 int improve_run(mgdp_vi *vi, int64_t *changed_out) {
     if (int rc = eval_buffers(vi)) return rc;
     MGDP_HIP(hipMemsetAsync(vi->d_eval + 1, 0, sizeof(unsigned long long), vi->stream));
-    if (vi->d.lava_mode == MGDP_LAVA_NODEATH) {
-        if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_nd<float>(vi) : launch_improve_nd<double>(vi)) return rc;
-    } else if (int rc = vi->d.dtype == MGDP_F32 ? launch_improve_m<float>(vi) : launch_improve_m<double>(vi)) {
-        return rc;
-    }
+    if (int rc = dispatch_eval<ImproveF>(vi)) return rc;
     unsigned long long n = 0;
     MGDP_HIP(hipMemcpyAsync(&n, vi->d_eval + 1, sizeof(n), hipMemcpyDeviceToHost, vi->stream));
     MGDP_HIP(hipStreamSynchronize(vi->stream));
@@ -1750,8 +1803,57 @@ int improve_run(mgdp_vi *vi, int64_t *changed_out) {
     return 0;
 }
 
-int policy_iteration_run(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out, int64_t *eval_sweeps_out,
-                         int64_t *changed_out, double *dv_out) {
+// ---- the four operations; `opts` as in eval_supported ----
+int evaluate_device(mgdp_vi *vi, bool opts, const int8_t *d_pi, int T, void *d_vt, int32_t *sweeps_out, double *dv_out,
+                    int32_t *converged_out) {
+    if (int rc = eval_supported(vi, "policy evaluation", opts)) return rc;
+    MGDP_CHECK((((uintptr_t)d_pi | (uintptr_t)d_vt) & 15u) == 0, MGDP_E_INVALID, "%s",
+               option_handle(vi) ? "policy / V_t: the device pointers must be 16-byte aligned"
+                                 : "policy: the device pointer must be 16-byte aligned");
+    MGDP_CHECK(d_pi || T == 1 || vi->d_pi_t, MGDP_E_INVALID,
+               "no per-step policy on the handle: create with MGDP_KEEP_POLICY_T, or pass pi");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    const int8_t *src = d_pi ? d_pi : (T == 1 ? vi->d_pi : vi->d_pi_t);
+    return eval_policy(vi, src, T, d_vt, sweeps_out, dv_out, converged_out);
+}
+
+int evaluate_host(mgdp_vi *vi, bool opts, const int8_t *pi, int T, void *V_t, int32_t *sweeps_out, double *dv_out,
+                  int32_t *converged_out) {
+    if (int rc = eval_supported(vi, "policy evaluation", opts)) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    const size_t BS = (size_t)vi->d.B * vi->S, HBS = (size_t)vi->d.horizon * BS;
+    int8_t *dst = vi->d_pi;
+    if (T != 1) {
+        if (!vi->d_pi_stage) MGDP_HIP(hipMalloc((void **)&vi->d_pi_stage, HBS));
+        dst = vi->d_pi_stage;
+    }
+    if (V_t && !vi->d_vt_stage) MGDP_HIP(hipMalloc(&vi->d_vt_stage, HBS * vi->tsize));
+    MGDP_HIP(hipMemcpyAsync(dst, pi, (size_t)T * BS, hipMemcpyHostToDevice, vi->stream));
+    MGDP_HIP(hipStreamSynchronize(vi->stream));  // the caller's buffer is free when this returns
+    if (int rc = eval_policy(vi, dst, T, V_t ? vi->d_vt_stage : nullptr, sweeps_out, dv_out, converged_out)) return rc;
+    if (V_t) {
+        MGDP_HIP(hipMemcpyAsync(V_t, vi->d_vt_stage, HBS * vi->tsize, hipMemcpyDeviceToHost, vi->stream));
+        MGDP_HIP(hipStreamSynchronize(vi->stream));
+    }
+    return 0;
+}
+
+int improve(mgdp_vi *vi, bool opts, int64_t *changed_out) {
+    if (int rc = greedy_supported(vi, "policy improvement", opts)) return rc;
+    MGDP_CHECK(vi->sweeps > 0, MGDP_E_INVALID, "policy improvement: no value function (solve or evaluate first)");
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
+    return improve_run(vi, changed_out);
+}
+
+int policy_iteration(mgdp_vi *vi, bool opts, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
+                     int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out) {
+    MGDP_CHECK(max_iters > 0, MGDP_E_INVALID, "max_iters must be > 0");
+    if (int rc = greedy_supported(vi, "policy iteration", opts)) return rc;
+    DeviceGuard guard(vi->d.device);
+    if (int rc = server_stop(vi)) return rc;
     const size_t BS = (size_t)vi->d.B * vi->S;
     if (pi0) {
         MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi0, BS, hipMemcpyHostToDevice, vi->stream));
@@ -1774,214 +1876,53 @@ int policy_iteration_run(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int3
     if (dv_out) *dv_out = dv;
     return 0;
 }
-
-// ---- evaluation under the handle options (kernels in vi_eval_opts.h) ----
-inline bool option_handle(const mgdp_vi *vi) { return vi->d.horizon > 0 || vi->d.lava_mode != MGDP_LAVA_TERMINAL; }
-
-int eval_opts_supported(const mgdp_vi *vi, const char *what) {
-    MGDP_CHECK(vi->cells_loaded, MGDP_E_INVALID, "no cells loaded");
-    MGDP_CHECK(vi->d.method == MGDP_METHOD_FUSED, MGDP_E_UNSUPPORTED, "%s runs on the fused method only", what);
-    MGDP_CHECK(vi->HW <= 1024, MGDP_E_UNSUPPORTED, "%s under horizon / lava options needs W*H <= 1024", what);
-    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    MGDP_CHECK(s.lds <= 160 * 1024, MGDP_E_UNSUPPORTED,
-               "%s: grid too large for the LDS-resident evaluation (%d B > 160 KiB)", what, s.lds);
-    MGDP_CHECK(vi->d.horizon <= kFhMaxH && vi->d.B <= kFhMaxB, MGDP_E_UNSUPPORTED,
-               "%s: horizon %d / batch %d exceed the policy error word", what, vi->d.horizon, vi->d.B);
-    return 0;
-}
-
-template <typename T, int MODEL, bool SLIP, bool ND, bool TI, bool VT>
-int launch_eval_fh_v(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
-    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    auto kern = vi_eval_fh_kernel<T, MODEL, SLIP, ND, TI, VT>;
-    constexpr int max_block = kEvalFhBlock<T, MODEL>;
-    MGDP_CHECK(s.block <= max_block, MGDP_E_UNSUPPORTED, "policy evaluation: %d cell slots exceed the kernel's %d threads",
-               s.block, max_block);
-    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
-    TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
-    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s),
-                          make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], pi_src, vi->d_pi, vi->d_kenv, vi->d_dvenv,
-                          vi->d_red, vi->d_ticket, vi->d_hout, vi->d_eval, (const T *)vi->d_rgoal, (T *)d_vt,
-                          vi->d.horizon, vi->d.B <= vi->kn.inkernel_max ? 1 : 0, next_host_epoch(vi));
-    MGDP_HIP(hipGetLastError());
-    vi->fresh = 0;
-    if (vi->d.B > vi->kn.inkernel_max) {
-        launch_reduce(vi, vi->d_hout);
-        MGDP_HIP(hipGetLastError());
-    }
-    return 0;
-}
-template <typename T, int MODEL, bool SLIP, bool ND, bool TI>
-int launch_eval_fh_t(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
-    return d_vt ? launch_eval_fh_v<T, MODEL, SLIP, ND, TI, true>(vi, pi_src, d_vt)
-                : launch_eval_fh_v<T, MODEL, SLIP, ND, TI, false>(vi, pi_src, d_vt);
-}
-template <typename T, bool TI>
-int launch_eval_fh_m(mgdp_vi *vi, const int8_t *pi_src, void *d_vt) {
-    if (vi->d.model == MGDP_MODEL_DOORKEY) return launch_eval_fh_t<T, MGDP_MODEL_DOORKEY, false, false, TI>(vi, pi_src, d_vt);
-    const bool slip = vi->d.slip_p >= 0.0, nd = vi->d.lava_mode == MGDP_LAVA_NODEATH;
-    if (slip) return nd ? launch_eval_fh_t<T, MGDP_MODEL_XYD, true, true, TI>(vi, pi_src, d_vt)
-                        : launch_eval_fh_t<T, MGDP_MODEL_XYD, true, false, TI>(vi, pi_src, d_vt);
-    return nd ? launch_eval_fh_t<T, MGDP_MODEL_XYD, false, true, TI>(vi, pi_src, d_vt)
-              : launch_eval_fh_t<T, MGDP_MODEL_XYD, false, false, TI>(vi, pi_src, d_vt);
-}
-int launch_eval_fh(mgdp_vi *vi, const int8_t *pi_src, bool ti, void *d_vt) {
-    if (vi->d.dtype == MGDP_F32) return ti ? launch_eval_fh_m<float, true>(vi, pi_src, d_vt) : launch_eval_fh_m<float, false>(vi, pi_src, d_vt);
-    return ti ? launch_eval_fh_m<double, true>(vi, pi_src, d_vt) : launch_eval_fh_m<double, false>(vi, pi_src, d_vt);
-}
-
-// The finite-horizon evaluation of the policy at d_src (T rows: 1 or H), one launch of exactly H sweeps.
-int eval_fh_run(mgdp_vi *vi, const int8_t *d_src, int T, void *d_vt, int32_t *sweeps_out, double *dv_out,
-                int32_t *converged_out) {
-    const int H = vi->d.horizon;
-    if (!vi->order_valid && vi->kn.order_src == 2 && vi->solves_since_load > 0 && order_eligible(vi))
-        if (int rc = learn_dispatch(vi)) return rc;
-    if (int rc = eval_buffers(vi)) return rc;
-    MGDP_HIP(hipMemsetAsync(vi->d_eval, 0xff, sizeof(unsigned long long), vi->stream));
-    vi->fresh = 1;
-    vi->cur = 0;
-    vi->k_done = vi->k_min = 0;
-    vi->k_done_valid = false;
-    vi->sweeps = vi->converged = 0;
-    vi->evaluated = true;  // whatever follows, kenv / dvenv / V are no longer a solve's
-    int32_t k = 0;
-    double dv = 0.0;
-    if (int rc = launch_eval_fh(vi, d_src, T != 1, d_vt)) return rc;
-    if (int rc = reduce_env(vi, &k, &dv)) return rc;
-    unsigned long long err = kEvalNoError;
-    MGDP_HIP(hipMemcpyAsync(&err, vi->d_eval, sizeof(err), hipMemcpyDeviceToHost, vi->stream));
-    MGDP_HIP(hipStreamSynchronize(vi->stream));
-    vi->k_done_valid = false;
-    if (err != kEvalNoError) {
-        const int row = (int)((err >> kFhRowShift) & (unsigned long long)(kFhMaxH - 1));
-        MGDP_CHECK(false, MGDP_E_INVALID, "policy: grid %d t %d state %d: action %d is outside [0, %d)",
-                   (int)(err >> kFhGridShift), T == 1 ? 0 : H - 1 - row, (int)((err >> 8) & 0x3fffu),
-                   (int)(int8_t)(err & 0xffu), vi->A);
-    }
-    MGDP_CHECK(k == H && vi->k_min == H, MGDP_E_INVALID, "evaluate: the horizon's %d sweeps ended at %d..%d", H, vi->k_min, k);
-    vi->k_done = k;
-    vi->sweeps = k;
-    vi->converged = 1;  // a finite horizon is exact after H sweeps
-    if (sweeps_out) *sweeps_out = k;
-    if (dv_out) *dv_out = dv;
-    if (converged_out) *converged_out = 1;
-    return 0;
-}
 }  // namespace
 }  // extern "C++"
 
 int mgdp_vi_evaluate_device(mgdp_vi *vi, const int8_t *d_pi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    if (int rc = eval_supported(vi, "policy evaluation")) return rc;
-    MGDP_CHECK(((uintptr_t)d_pi & 15u) == 0, MGDP_E_INVALID, "policy: the device pointer must be 16-byte aligned");
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    return eval_run(vi, d_pi ? d_pi : vi->d_pi, sweeps_out, dv_out, converged_out);
+    return evaluate_device(vi, false, d_pi, 1, nullptr, sweeps_out, dv_out, converged_out);
 }
 
 int mgdp_vi_evaluate(mgdp_vi *vi, const int8_t *pi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {
     MGDP_CHECK(vi && pi, MGDP_E_INVALID, "null argument");
-    if (int rc = eval_supported(vi, "policy evaluation")) return rc;
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    MGDP_HIP(hipMemcpyAsync(vi->d_pi, pi, (size_t)vi->d.B * vi->S, hipMemcpyHostToDevice, vi->stream));
-    MGDP_HIP(hipStreamSynchronize(vi->stream));  // the caller's buffer is free when this returns
-    return eval_run(vi, vi->d_pi, sweeps_out, dv_out, converged_out);
+    return evaluate_host(vi, false, pi, 1, nullptr, sweeps_out, dv_out, converged_out);
 }
 
 int mgdp_vi_improve(mgdp_vi *vi, int64_t *changed_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    if (int rc = eval_supported(vi, "policy improvement")) return rc;
-    MGDP_CHECK(vi->sweeps > 0, MGDP_E_INVALID, "policy improvement: no value function (solve or evaluate first)");
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    return improve_run(vi, changed_out);
+    return improve(vi, false, changed_out);
 }
 
 int mgdp_vi_policy_iteration(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
                              int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    MGDP_CHECK(max_iters > 0, MGDP_E_INVALID, "max_iters must be > 0");
-    if (int rc = eval_supported(vi, "policy iteration")) return rc;
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    return policy_iteration_run(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
+    return policy_iteration(vi, false, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
 }
 
 int mgdp_vi_evaluate_opts_device(mgdp_vi *vi, const int8_t *d_pi, int32_t T, void *d_V_t, int32_t *sweeps_out,
                                  double *dv_out, int32_t *converged_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    const int H = vi->d.horizon;
-    MGDP_CHECK(T == 1 || (H > 0 && T == H), MGDP_E_INVALID,
-               "policy rows T = %d: 1 (stationary)%s", T, H > 0 ? " or the handle's horizon" : " on a horizon-0 handle");
-    MGDP_CHECK(!(d_V_t && H == 0), MGDP_E_INVALID, "V_t needs a finite horizon");
-    if (!option_handle(vi)) return mgdp_vi_evaluate_device(vi, d_pi, sweeps_out, dv_out, converged_out);
-    if (int rc = eval_opts_supported(vi, "policy evaluation")) return rc;
-    MGDP_CHECK((((uintptr_t)d_pi | (uintptr_t)d_V_t) & 15u) == 0, MGDP_E_INVALID,
-               "policy / V_t: the device pointers must be 16-byte aligned");
-    MGDP_CHECK(d_pi || T == 1 || vi->d_pi_t, MGDP_E_INVALID,
-               "no per-step policy on the handle: create with MGDP_KEEP_POLICY_T, or pass pi");
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    const int8_t *src = d_pi ? d_pi : (T == 1 ? vi->d_pi : vi->d_pi_t);
-    if (H == 0) return eval_run(vi, src, sweeps_out, dv_out, converged_out);
-    return eval_fh_run(vi, src, T, d_V_t, sweeps_out, dv_out, converged_out);
+    if (int rc = eval_rows_supported(vi, T, d_V_t)) return rc;
+    return evaluate_device(vi, true, d_pi, T, d_V_t, sweeps_out, dv_out, converged_out);
 }
 
 int mgdp_vi_evaluate_opts(mgdp_vi *vi, const int8_t *pi, int32_t T, void *V_t, int32_t *sweeps_out, double *dv_out,
                           int32_t *converged_out) {
     MGDP_CHECK(vi && pi, MGDP_E_INVALID, "null argument");
-    const int H = vi->d.horizon;
-    MGDP_CHECK(T == 1 || (H > 0 && T == H), MGDP_E_INVALID,
-               "policy rows T = %d: 1 (stationary)%s", T, H > 0 ? " or the handle's horizon" : " on a horizon-0 handle");
-    MGDP_CHECK(!(V_t && H == 0), MGDP_E_INVALID, "V_t needs a finite horizon");
-    if (!option_handle(vi)) return mgdp_vi_evaluate(vi, pi, sweeps_out, dv_out, converged_out);
-    if (int rc = eval_opts_supported(vi, "policy evaluation")) return rc;
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    const size_t BS = (size_t)vi->d.B * vi->S;
-    int8_t *dst = vi->d_pi;
-    if (T != 1) {
-        if (!vi->d_pi_stage) MGDP_HIP(hipMalloc((void **)&vi->d_pi_stage, (size_t)H * BS));
-        dst = vi->d_pi_stage;
-    }
-    if (V_t && !vi->d_vt_stage) MGDP_HIP(hipMalloc(&vi->d_vt_stage, (size_t)H * BS * vi->tsize));
-    MGDP_HIP(hipMemcpyAsync(dst, pi, (size_t)T * BS, hipMemcpyHostToDevice, vi->stream));
-    MGDP_HIP(hipStreamSynchronize(vi->stream));  // the caller's buffer is free when this returns
-    if (H == 0) return eval_run(vi, dst, sweeps_out, dv_out, converged_out);
-    if (int rc = eval_fh_run(vi, dst, T, V_t ? vi->d_vt_stage : nullptr, sweeps_out, dv_out, converged_out)) return rc;
-    if (V_t) {
-        MGDP_HIP(hipMemcpyAsync(V_t, vi->d_vt_stage, (size_t)H * BS * vi->tsize, hipMemcpyDeviceToHost, vi->stream));
-        MGDP_HIP(hipStreamSynchronize(vi->stream));
-    }
-    return 0;
+    if (int rc = eval_rows_supported(vi, T, V_t)) return rc;
+    return evaluate_host(vi, true, pi, T, V_t, sweeps_out, dv_out, converged_out);
 }
 
 int mgdp_vi_improve_opts(mgdp_vi *vi, int64_t *changed_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    if (!option_handle(vi)) return mgdp_vi_improve(vi, changed_out);
-    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED,
-               "policy improvement is refused on a finite horizon: its greedy step is the solve itself");
-    if (int rc = eval_opts_supported(vi, "policy improvement")) return rc;
-    MGDP_CHECK(vi->sweeps > 0, MGDP_E_INVALID, "policy improvement: no value function (solve or evaluate first)");
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    return improve_run(vi, changed_out);
+    return improve(vi, true, changed_out);
 }
 
 int mgdp_vi_policy_iteration_opts(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
                                   int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
-    if (!option_handle(vi))
-        return mgdp_vi_policy_iteration(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
-    MGDP_CHECK(max_iters > 0, MGDP_E_INVALID, "max_iters must be > 0");
-    MGDP_CHECK(vi->d.horizon == 0, MGDP_E_UNSUPPORTED,
-               "policy iteration is refused on a finite horizon: its greedy step is the solve itself");
-    if (int rc = eval_opts_supported(vi, "policy iteration")) return rc;
-    DeviceGuard guard(vi->d.device);
-    if (int rc = server_stop(vi)) return rc;
-    return policy_iteration_run(vi, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
+    return policy_iteration(vi, true, pi0, max_iters, iters_out, eval_sweeps_out, changed_out, dv_out);
 }
 
 int mgdp_vi_solve_last(mgdp_vi *vi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {

@@ -335,8 +335,10 @@ vi_eval_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__rest
 // that pi(s) stays when Q(s, pi(s)) equals the maximum (so "no state changed" is a valid stop of policy
 // iteration).  Q is the per-action form of xyd_step / dk_step (slip: p*Qd[a] + tail).  Returns the
 // packed new lanes and adds the changed valid states to n.  A current lane outside [0, A) never keeps.
+// ND: the NoDeath Q -- the move into lava carries dc; Q may be negative, and the
+// comparisons are plain either way.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool SLIP>
+template <typename T, bool SLIP, bool ND>
 __device__ __forceinline__ uint32_t xyd_improve_step(const XydTopo<T> &tp, const Coef<T> &cf, const V4<T> &own,
                                                      const T (&nbv)[4], uint32_t old, unsigned int &n) {
     T gv[4];
@@ -345,7 +347,8 @@ __device__ __forceinline__ uint32_t xyd_improve_step(const XydTopo<T> &tp, const
     uint32_t pk = 0;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        const T qM = cf.g * nbv[d];
+        T qM = cf.g * nbv[d];
+        if constexpr (ND) qM = ((tp.lavaF >> d) & 1u) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
         const T qF = ((tp.term >> d) & 1u) ? tp.tq[d] : qM;
         const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
         T a0 = qL, a1 = qR, a2 = qF, a3 = qS;  // Q of actions 0..3 (4..6 equal action 3)
@@ -421,8 +424,9 @@ __device__ __forceinline__ Pk16 dk_improve_step(const DkTopo &tp, const Coef<T> 
 
 // One pass per grid over the V in HBM: the grid's V row (cell-major) and cells are staged into LDS,
 // each thread improves its cells' lanes in place in pi, and the workgroup adds its count of changed
-// states to *changed (one vector atomic per workgroup that changed anything).
-template <typename T, int MODEL, bool SLIP>
+// states to *changed (one vector atomic per workgroup that changed anything).  ND (XYD only): the
+// NoDeath topology and Q.
+template <typename T, int MODEL, bool SLIP, bool ND>
 __global__ void __launch_bounds__(256)
 vi_improve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, const T *__restrict__ V,
                   int8_t *__restrict__ pi, unsigned long long *__restrict__ changed) {
@@ -439,12 +443,12 @@ vi_improve_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, const 
     unsigned int n = 0;
     for (int c = threadIdx.x; c < geo.HW; c += blockDim.x) {
         if constexpr (MODEL == MGDP_MODEL_XYD) {
-            const XydTopo<T> tp = xyd_topo<T>(cl, geo, c);
+            const XydTopo<T> tp = xyd_topo<T, ND>(cl, geo, c);
             const V4<T> own = *reinterpret_cast<const V4<T> *>(Vs + c * 4);
             T nbv[4];
             xyd_load_nb(tp, Vs, nbv);
             uint32_t *p = reinterpret_cast<uint32_t *>(pi + vb + c * 4);
-            *p = xyd_improve_step<T, SLIP>(tp, cf, own, nbv, *p, n);
+            *p = xyd_improve_step<T, SLIP, ND>(tp, cf, own, nbv, *p, n);
         } else {
             const DkTopo tp = dk_topo(cl, geo, c);
             T own[16];

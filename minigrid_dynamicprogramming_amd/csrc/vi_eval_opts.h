@@ -1,8 +1,8 @@
 // vi_eval_opts.h -- policy evaluation under the handle options: V^pi on NoDeath
 // lava (discounted, the protocol of vi_eval_kernel), the finite-horizon backward induction of a
-// stationary or time-indexed policy (exactly H sweeps, no stop test), and the greedy improvement on
-// the NoDeath Q.  Part of the single translation unit vi.hip (included after vi_eval.h).  Option
-// handles hold W*H <= 1024 (mgdp_vi_create), so every kernel here is one thread per cell, topology
+// stationary or time-indexed policy (exactly H sweeps, no stop test).  (The greedy improvement on the
+// NoDeath Q is vi_improve_kernel's ND form, vi_eval.h.)  Part of the single translation unit vi.hip
+// (included after vi_eval.h).  Option handles hold W*H <= 1024 (mgdp_vi_create), so every kernel here is one thread per cell, topology
 // and lanes in registers, both V tiles in LDS (smem_layout's direction-major tiles).
 // The steps are the per-action forms Qd = done ? R : fl(R + fl(g*V[s'])) of the oracle's tables: V may
 // be negative under NoDeath, so none of xyd_step's value-only shortcuts (max with +0, an invalid front
@@ -465,77 +465,6 @@ vi_eval_nd_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__r
     }
     if (in_kernel_reduce)
         fused_reduce(red, ticket, host_out, k, dvl, reinterpret_cast<unsigned int *>(slots + 16), epoch, false, tid);
-}
-
-// xyd_improve_step on the NoDeath Q (the lava move carries dc; Q may be negative: plain comparisons)
-template <typename T, bool SLIP>
-__device__ __forceinline__ uint32_t xyd_improve_step_nd(const XydTopo<T> &tp, const Coef<T> &cf, const V4<T> &own,
-                                                        const T (&nbv)[4], uint32_t old, unsigned int &n) {
-    T gv[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) gv[d] = cf.g * own.v[d];
-    uint32_t pk = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const T qM = ((tp.lavaF >> d) & 1u) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
-        const T qF = ((tp.term >> d) & 1u) ? tp.tq[d] : qM;
-        const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T a0 = qL, a1 = qR, a2 = qF, a3 = qS;  // Q of actions 0..3 (4..6 equal action 3)
-        if (SLIP) {
-            T s6 = qL + qR;
-            s6 = s6 + qF;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            const T tail = cf.c * s6;
-            a0 = cf.p * qL + tail;
-            a1 = cf.p * qR + tail;
-            a2 = cf.p * qF + tail;
-            a3 = cf.p * qS + tail;
-        }
-        uint32_t arg = 0;
-        T best = a0;
-        if (a1 > best) { best = a1; arg = 1; }
-        if (a2 > best) { best = a2; arg = 2; }
-        if (a3 > best) { best = a3; arg = 3; }
-        const uint32_t cur = (old >> (8 * d)) & 0xffu;
-        const T qc = cur == 0u ? a0 : (cur == 1u ? a1 : (cur == 2u ? a2 : a3));
-        if (cur < 7u && qc == best) arg = cur;
-        if (tp.valid && arg != cur) ++n;
-        pk |= (tp.valid ? arg : 0xffu) << (8 * d);
-    }
-    return pk;
-}
-
-// vi_improve_kernel on the NoDeath topology (XYD)
-template <typename T, bool SLIP>
-__global__ void __launch_bounds__(256)
-vi_improve_nd_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, const T *__restrict__ V,
-                     int8_t *__restrict__ pi, unsigned long long *__restrict__ changed) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ unsigned int cnt;
-    T *Vs = reinterpret_cast<T *>(smem);
-    uint8_t *cl = reinterpret_cast<uint8_t *>(smem + geo.S * (int)sizeof(T));
-    const int e = blockIdx.x;
-    const long long vb = (long long)e * geo.S;
-    copy16(Vs, V + vb, geo.S * (int)sizeof(T));
-    copy16(cl, cells + (long long)e * geo.HWp, geo.HWp);
-    if (threadIdx.x == 0) cnt = 0u;
-    __syncthreads();
-    unsigned int n = 0;
-    for (int c = threadIdx.x; c < geo.HW; c += blockDim.x) {
-        const XydTopo<T> tp = xyd_topo<T, true>(cl, geo, c);
-        const V4<T> own = *reinterpret_cast<const V4<T> *>(Vs + c * 4);
-        T nbv[4];
-        xyd_load_nb(tp, Vs, nbv);
-        uint32_t *p = reinterpret_cast<uint32_t *>(pi + vb + c * 4);
-        *p = xyd_improve_step_nd<T, SLIP>(tp, cf, own, nbv, *p, n);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&cnt, n);
-    __syncthreads();
-    if (threadIdx.x == 0 && cnt) atomicAdd(changed, (unsigned long long)cnt);
 }
 
 }  // namespace mgdp

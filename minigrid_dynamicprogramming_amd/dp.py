@@ -282,19 +282,50 @@ class ValueIteration:
         self._live = self._out
         return self._out[0].value
 
-    # -- policy evaluation / improvement / policy iteration
+    # -- policy evaluation / improvement / policy iteration (DESIGN.md sections 13 and 19)
     def _check_policy(self, pi) -> np.ndarray:
         """(B, S) int8 action lanes (any integer dtype that fits), checked before any device work."""
+        return self._check_policy_opts(pi, rows=False)[0]
+
+    def _check_policy_opts(self, pi, rows: bool = True) -> tuple[np.ndarray, int]:
+        """_check_policy that with `rows` also takes (H, B, S) on a finite-horizon handle: (array, rows T)."""
         a = np.asarray(pi)
         if a.dtype.kind not in "iu":
             raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
-        if a.shape != (self.B, self.S):
-            raise ValueError(f"policy of shape {a.shape} does not match the handle's {(self.B, self.S)}")
+        rows = rows and self.horizon > 0
+        if a.shape == (self.B, self.S):
+            T = 1
+        elif rows and a.shape == (self.horizon, self.B, self.S):
+            T = self.horizon
+        else:
+            want = f"{(self.B, self.S)}" + (f" or {(self.horizon, self.B, self.S)}" if rows else "")
+            raise ValueError(f"policy of shape {a.shape} does not match the handle's {want}")
         if a.dtype != np.int8:
             if a.size and (a.min() < -128 or a.max() > 127):
                 raise ValueError("policy entries do not fit int8 action lanes")
             a = a.astype(np.int8)
-        return np.ascontiguousarray(a)
+        return np.ascontiguousarray(a), T
+
+    def _call_result(self, name: str, *args) -> int:
+        """`name`(handle, *args, &sweeps, &dv, &converged): the three become the handle's result."""
+        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
+        _lib.check(getattr(self.L, name)(self.h, *args, ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)), name)
+        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
+        return self.sweeps
+
+    def _call_policy_iteration(self, name: str, pi0, max_iters) -> dict:
+        a = None if pi0 is None else self._check_policy(pi0)
+        if int(max_iters) <= 0:
+            raise ValueError("max_iters must be > 0")
+        it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
+        _lib.check(getattr(self.L, name)(self.h, None if a is None else _lib.ptr(a), int(max_iters), ctypes.byref(it),
+                                         ctypes.byref(tot), ctypes.byref(ch), ctypes.byref(dv)), name)
+        # converged of the last evaluation: dv < tol unless max_sweeps capped it
+        self.dv = dv.value
+        self.converged = dv.value < self.tol
+        # the last evaluation's K is the largest per-grid count (a grid below K ended at a fixed point)
+        self.sweeps = int(self.grid_sweeps().max())
+        return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
 
     def evaluate(self, pi) -> int:
         """V^pi of a policy (mgdp_vi_evaluate): pi is (B, S) int8 in policy()'s state order and action
@@ -303,22 +334,13 @@ class ValueIteration:
         stopping rule; values(), policy(), grid_sweeps() and result() then describe the evaluation.
         run_to / sweep / resume need a reset() afterwards; solve() works as before."""
         a = self._check_policy(pi)
-        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
-        _lib.check(self.L.mgdp_vi_evaluate(self.h, _lib.ptr(a), ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
-                   "mgdp_vi_evaluate")
-        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
-        return self.sweeps
+        return self._call_result("mgdp_vi_evaluate", _lib.ptr(a))
 
     def evaluate_device(self, pi_ptr: int | None = None) -> int:
         """evaluate() of a policy in device memory (mgdp_vi_evaluate_device): B*S int8 at `pi_ptr`
         (16-byte aligned, e.g. a torch int8 tensor's data_ptr()); None evaluates the handle's own pi
         buffer -- pi* right after a solve()."""
-        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
-        _lib.check(self.L.mgdp_vi_evaluate_device(self.h, None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)),
-                                                  ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
-                   "mgdp_vi_evaluate_device")
-        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
-        return self.sweeps
+        return self._call_result("mgdp_vi_evaluate_device", None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)))
 
     def improve(self) -> int:
         """Greedy improvement on the handle's V (mgdp_vi_improve): pi(s) <- argmax_a Q(s, a), lowest
@@ -332,39 +354,9 @@ class ValueIteration:
         """Policy iteration (mgdp_vi_policy_iteration) from pi0 ((B, S) int8; None: "forward" on every
         valid state): evaluate from V_0 = 0, improve, until no state changes or max_iters.  Returns
         dict(iters, eval_sweeps, changed, dv); values() is the last evaluation's V, policy() the final pi."""
-        a = None if pi0 is None else self._check_policy(pi0)
-        if int(max_iters) <= 0:
-            raise ValueError("max_iters must be > 0")
-        it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
-        _lib.check(self.L.mgdp_vi_policy_iteration(self.h, None if a is None else _lib.ptr(a), int(max_iters),
-                                                   ctypes.byref(it), ctypes.byref(tot), ctypes.byref(ch), ctypes.byref(dv)),
-                   "mgdp_vi_policy_iteration")
-        # converged of the last evaluation: dv < tol unless max_sweeps capped it
-        self.dv = dv.value
-        self.converged = dv.value < self.tol
-        # the last evaluation's K is the largest per-grid count (a grid below K ended at a fixed point)
-        self.sweeps = int(self.grid_sweeps().max())
-        return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
+        return self._call_policy_iteration("mgdp_vi_policy_iteration", pi0, max_iters)
 
     # -- the same under horizon / lava="nodeath" (DESIGN.md section 19)
-    def _check_policy_opts(self, pi) -> tuple[np.ndarray, int]:
-        """(B, S) or (H, B, S) int8 action lanes, checked before any device work: (array, rows T)."""
-        a = np.asarray(pi)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
-        if a.shape == (self.B, self.S):
-            T = 1
-        elif self.horizon > 0 and a.shape == (self.horizon, self.B, self.S):
-            T = self.horizon
-        else:
-            want = f"{(self.B, self.S)}" + (f" or {(self.horizon, self.B, self.S)}" if self.horizon > 0 else "")
-            raise ValueError(f"policy of shape {a.shape} does not match the handle's {want}")
-        if a.dtype != np.int8:
-            if a.size and (a.min() < -128 or a.max() > 127):
-                raise ValueError("policy entries do not fit int8 action lanes")
-            a = a.astype(np.int8)
-        return np.ascontiguousarray(a), T
-
     def evaluate_opts(self, pi, values_t: bool = False) -> int:
         """evaluate() on any handle (mgdp_vi_evaluate_opts).  lava="nodeath", horizon 0: the discounted
         V^pi on the NoDeath tables.  horizon H > 0: backward induction, exactly H sweeps, of a stationary
@@ -376,14 +368,10 @@ class ValueIteration:
         if values_t and self.horizon == 0:
             raise ValueError("values_t needs a finite horizon")
         vt = np.empty((self.horizon, self.B, self.S), self.np_dtype) if values_t else None
-        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
         self._values_t = None
-        _lib.check(self.L.mgdp_vi_evaluate_opts(self.h, _lib.ptr(a), T, None if vt is None else _lib.ptr(vt),
-                                                ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)),
-                   "mgdp_vi_evaluate_opts")
+        k = self._call_result("mgdp_vi_evaluate_opts", _lib.ptr(a), T, None if vt is None else _lib.ptr(vt))
         self._values_t = vt
-        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
-        return self.sweeps
+        return k
 
     def values_t(self) -> np.ndarray:
         """(H, B, S): every V_t of the last evaluate_opts(pi, values_t=True)."""
@@ -401,14 +389,9 @@ class ValueIteration:
             raise ValueError(f"policy rows T = {T}: 1 or the handle's horizon ({self.horizon})")
         if values_t_ptr is not None and self.horizon == 0:
             raise ValueError("values_t needs a finite horizon")
-        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
         self._values_t = None
-        _lib.check(self.L.mgdp_vi_evaluate_opts_device(
-            self.h, None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)), T,
-            None if values_t_ptr is None else ctypes.c_void_p(int(values_t_ptr)),
-            ctypes.byref(k), ctypes.byref(dv), ctypes.byref(conv)), "mgdp_vi_evaluate_opts_device")
-        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
-        return self.sweeps
+        return self._call_result("mgdp_vi_evaluate_opts_device", None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)),
+                                 T, None if values_t_ptr is None else ctypes.c_void_p(int(values_t_ptr)))
 
     def improve_opts(self) -> int:
         """improve() on a plain or lava="nodeath" handle (mgdp_vi_improve_opts); refused on a finite horizon."""
@@ -419,17 +402,7 @@ class ValueIteration:
     def policy_iteration_opts(self, pi0=None, max_iters: int = 1000) -> dict:
         """policy_iteration() on a plain or lava="nodeath" handle (mgdp_vi_policy_iteration_opts); refused
         on a finite horizon (its greedy step is the solve itself)."""
-        a = None if pi0 is None else self._check_policy(pi0)
-        if int(max_iters) <= 0:
-            raise ValueError("max_iters must be > 0")
-        it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
-        _lib.check(self.L.mgdp_vi_policy_iteration_opts(self.h, None if a is None else _lib.ptr(a), int(max_iters),
-                                                        ctypes.byref(it), ctypes.byref(tot), ctypes.byref(ch),
-                                                        ctypes.byref(dv)), "mgdp_vi_policy_iteration_opts")
-        self.dv = dv.value
-        self.converged = dv.value < self.tol
-        self.sweeps = int(self.grid_sweeps().max())
-        return {"iters": it.value, "eval_sweeps": tot.value, "changed": ch.value, "dv": dv.value}
+        return self._call_policy_iteration("mgdp_vi_policy_iteration_opts", pi0, max_iters)
 
     # sweeps / dv / converged of the last result: read from solve()'s outputs while they are current
     def _result_attr(self, i, name):
@@ -615,11 +588,7 @@ class ValueIteration:
         if V.shape != (self.B, self.S):
             raise ValueError(f"checkpoint V of shape {V.shape} does not match the handle's {(self.B, self.S)}")
         V = np.ascontiguousarray(V)
-        k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
-        _lib.check(self.L.mgdp_vi_resume(self.h, _lib.ptr(V), int(ckpt["sweeps"]), float(ckpt["dv"]), ctypes.byref(k),
-                                         ctypes.byref(dv), ctypes.byref(conv)), "mgdp_vi_resume")
-        self.sweeps, self.dv, self.converged = k.value, dv.value, bool(conv.value)
-        return self.sweeps
+        return self._call_result("mgdp_vi_resume", _lib.ptr(V), int(ckpt["sweeps"]), float(ckpt["dv"]))
 
     @staticmethod
     def save_checkpoint(path, ckpt: dict) -> None:

@@ -15,8 +15,10 @@ import pytest
 
 import minigrid_dynamicprogramming_amd as mg
 from minigrid_dynamicprogramming_amd.dp import n_actions, state_index
+from oracle import oracle
 from tests import rollout_ref as rr
 from tests.policy_opts_ref import PolicyOptsRef, lava_entries
+from tests.policy_ref import PolicyRef
 
 pytestmark = pytest.mark.gpu
 
@@ -445,6 +447,66 @@ def test_plain_handle_gives_the_plain_results(model, env_id, slip):
     np.testing.assert_array_equal(vi.values(), Va)
     with pytest.raises(ValueError, match="finite horizon"):
         vi.evaluate_opts(pol, values_t=True)
+    vi.close()
+
+
+@functools.lru_cache(maxsize=None)
+def room40():
+    """Two 40 x 40 rooms, 1600 cells each: above the option kernels' 1024, so the evaluation is the strided
+    form of vi_eval_kernel (about 51 KiB of LDS in fp32).  One empty with a goal; one with a few walls and
+    a lava cell before its goal."""
+    out = []
+    for b in range(2):
+        c = np.full((40, 40), 1, np.uint8)
+        c[0, :] = c[-1, :] = c[:, 0] = c[:, -1] = 2
+        c[38, 38] = 8
+        if b:
+            c[12, 1:30] = 2
+            c[25, 8:39] = 2
+            c[5:20, 33] = 2
+            c[37, 30] = 9
+        out.append(c)
+    return np.stack(out)
+
+
+def test_plain_handle_above_1024_cells_is_the_same_through_both_families():
+    """A plain handle is not bound by the option handles' W*H <= 1024: the *_opts names reach the same
+    strided evaluation as the plain names, result for result, and both match the restatement bit for bit."""
+    cells, B = room40(), 2
+    vi = handle(cells, "xyd", dtype="f32", gamma=0.99)
+    ref = PolicyRef(0, cells, gamma=0.99, dtype="f32")
+    # pi* with a seeded 2 % of the lanes replaced: most states still reach the goal, later and on other paths
+    # (V != 0 on thousands of states, 128 sweeps, the two grids stop at different sweeps)
+    rng = np.random.default_rng(40)
+    pol = oracle.value_iteration(0, cells, dtype="f32", gamma=0.99)["pi"].copy()
+    swap = rng.random((B, vi.S)) < 0.02
+    pol[swap] = rng.integers(0, n_actions("xyd"), int(swap.sum()))
+    r = ref.evaluate(pol)
+
+    def state():
+        return vi.values(), vi.policy(), vi.grid_sweeps(), vi.sweeps, vi.dv
+
+    def same(a, b):
+        for x, y in zip(a[:3], b[:3]):
+            np.testing.assert_array_equal(x, y)
+        assert a[3:] == b[3:]
+
+    want = (r["V"], r["pi"], r["grid_sweeps"], r["sweeps"], r["dv"])
+    for fn in (vi.evaluate, vi.evaluate_opts):
+        assert fn(pol) == r["sweeps"] and vi.converged == r["converged"]
+        same(state(), want)
+    for fn in (vi.evaluate_device, vi.evaluate_opts_device):  # the handle's own buffer: pol, normalised
+        assert fn(None) == r["sweeps"]
+        same(state(), want)
+    got = []
+    for fn in (vi.improve, vi.improve_opts):
+        vi.evaluate(pol)
+        got.append((fn(), state()))
+    assert got[0][0] == got[1][0] > 0
+    same(got[0][1], got[1][1])
+    got = [(fn(pol, max_iters=3), state()) for fn in (vi.policy_iteration, vi.policy_iteration_opts)]
+    assert got[0][0] == got[1][0]
+    same(got[0][1], got[1][1])
     vi.close()
 
 

@@ -6,7 +6,8 @@ kernel microseconds, from the handle's HIP events, of
     c  b with V_t                       plus one row of values written per sweep
     d  evaluate_opts_device(None, T=1)  a stationary pi: lanes in registers, nothing per sweep
 
-The sides alternate within a repetition; the figure is the median of --reps repetitions with min-max.
+The sides alternate within a repetition; the figure is the median of --reps repetitions with min-max
+(and the median wall time of the whole call).
 b (and c) must reproduce the solve's V_0 bit for bit (checked).  Also prints the bytes of the pi_t read
 and of the V_t write and their time at the streaming-copy rate, so the bound that applies can be named.
 The prefetch distance is a compile-time constant (MGDP_EVAL_PF): build one library per distance
@@ -19,6 +20,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -68,11 +70,14 @@ def main():
             assert np.array_equal(d_vt[0].cpu().numpy(), V)
         vi.enable_timing(True)
         us = {s: [] for s in args.sides}
+        wall = {s: [] for s in args.sides}
         launches = {}
         for _ in range(args.reps):
             for s in args.sides:  # alternating: every side sees the same clocks and neighbours
                 ms0, n0 = vi.kernel_time()
+                t = time.perf_counter()
                 calls[s]()
+                wall[s].append((time.perf_counter() - t) * 1e6)
                 ms1, n1 = vi.kernel_time()
                 us[s].append((ms1 - ms0) * 1e3)
                 launches[s] = n1 - n0
@@ -85,6 +90,7 @@ def main():
             rec[f"{s}_us_min_max"] = [round(min(us[s]), 1), round(max(us[s]), 1)]
             rec[f"{s}_us_per_sweep"] = round(float(np.median(us[s])) / H, 4)
             rec[f"{s}_launches"] = launches[s]
+            rec[f"{s}_wall_us"] = round(float(np.median(wall[s])), 1)  # the whole call, host side included
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
