@@ -317,6 +317,42 @@ int mgdp_vi_improve_opts(mgdp_vi *vi, int64_t *changed_out);
 int mgdp_vi_policy_iteration_opts(mgdp_vi *vi, const int8_t *pi0, int32_t max_iters, int32_t *iters_out,
                                   int64_t *eval_sweeps_out, int64_t *changed_out, double *dv_out);
 
+/* The forward pass of a policy (additive entry points, the ABI version is unchanged):
+ * mu_{t+1} = P_pi^T mu_t, the transpose of the evaluation's sweep, over exactly N steps with no stop test.
+ * XYD handles of W*H <= 1024 with any options (slip as the handle was created, MGDP_LAVA_NODEATH, horizon;
+ * float or double); DoorKey and larger grids are MGDP_E_UNSUPPORTED (DoorKey's DP has no slip: its forward
+ * pass from one start is mgdp_envs_rollout with a trace).  The call reads the handle's cells and options
+ * only: V, pi, the per-grid sweeps and the protocol state are untouched, it works before any solve, and a
+ * later mgdp_vi_solve is the one of a fresh handle.  mgdp_vi_kernel_time counts the launch.
+ *   N: the horizon on a finite-horizon handle (n_steps 0 or the horizon); on a horizon-0 handle n_steps,
+ *     1 <= n_steps <= 2^20.
+ *   pi: stationary (T = 1, [B][S]) or time-indexed (T = N, [N][B][S], t-major: row t is the policy applied
+ *     at step_count t, the layout of mgdp_vi_get_policy_t and mgdp_envs_rollout); any other T is
+ *     MGDP_E_INVALID.  A lane outside [0, 7) on a valid state is MGDP_E_INVALID; the message names the lowest
+ *     offending grid, within it the smallest offending t (the first row the pass reaches) and within that
+ *     row the lowest offending state; that grid steps no further and the handle stays usable.
+ *   start / mu0: exactly one is non-NULL.  start: B int32 state indices, mu_0 one-hot with mass 1; an index
+ *     outside [0, S) or on an absorbing state (wall, goal, terminal lava) is MGDP_E_INVALID.  mu0: [B][S] of
+ *     the handle's dtype; non-zero mass on an absorbing state is MGDP_E_INVALID.  Both messages name the
+ *     lowest grid and its lowest state.
+ *   Outputs, each [B][S] of the handle's dtype, +0 on walls (occ, ret and mu_t may be NULL):
+ *     mu   mu_N on valid states; on goal and terminal-lava states the mass absorbed there.
+ *     occ  sum over t < N of fl(disc[t] * mu_t[s]) on valid states, disc[0] = 1, disc[t+1] = fl(gamma *
+ *          disc[t]): the discounted visitation (d^pi up to normalisation); +0 on absorbing states.
+ *     ret  the discounted reward collected on entering: on goal states sum of fl(wg[t] * inflow), wg[t] =
+ *          fl(disc[t] * _reward(t+1, H)) on a finite horizon, else disc[t]; on NoDeath lava states sum of
+ *          fl(fl(disc[t] * death_cost) * inflow); +0 elsewhere.  The sum over a grid is <mu_0, V_0^pi>.
+ *     mu_t every mu_t, t = 0..N-1, as [N][B][S], t-major: row t holds mu_t on valid states and the mass
+ *          absorbed before step t on terminal ones.
+ *   Every product and sum is one rounding in the handle's dtype, in the order DESIGN.md section 21 states.
+ *   mgdp_vi_occupancy: host pointers, through device staging allocated at the first call that needs it.
+ *   mgdp_vi_occupancy_device: device pointers (16-byte aligned, start 4-byte; complete before the call), on
+ *     the handle's stream; the results are complete when it returns. */
+int mgdp_vi_occupancy(mgdp_vi *vi, const int8_t *pi, int32_t T, const int32_t *start, const void *mu0, int32_t n_steps,
+                      void *mu, void *occ, void *ret, void *mu_t);
+int mgdp_vi_occupancy_device(mgdp_vi *vi, const int8_t *d_pi, int32_t T, const int32_t *d_start, const void *d_mu0,
+                             int32_t n_steps, void *d_mu, void *d_occ, void *d_ret, void *d_mu_t);
+
 /* Results (host).  V: B*S of float or double per dtype; pi: B*S int8 (-1 = absorbing state). */
 int mgdp_vi_get_values(mgdp_vi *vi, void *V);
 int mgdp_vi_get_policy(mgdp_vi *vi, int8_t *pi);

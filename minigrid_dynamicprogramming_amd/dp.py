@@ -118,6 +118,46 @@ class VIResult:
         return DOORKEY_ACTIONS[lane] if self.model == "doorkey" else lane
 
 
+@dataclass
+class OccupancyResult:
+    """The forward pass of a policy (ValueIteration.occupancy).  Planes are (B, S) in
+    the handle's dtype, +0 on walls; the derived arrays are (B,) float64 sums over masks taken from the cells
+    (None when the cells were installed from device memory)."""
+    mu: np.ndarray              # mu_N on valid states; on goal / terminal-lava states the mass absorbed there
+    occ: np.ndarray             # sum_t disc[t] * mu_t: the discounted visitation (d^pi up to normalisation)
+    ret: np.ndarray             # the discounted reward collected on entering goal (and NoDeath lava) states
+    mu_t: np.ndarray | None     # (N, B, S) every mu_t, with every_step=True
+    n_steps: int
+    model: str
+    W: int
+    H: int
+    p_goal: np.ndarray | None = None           # mass on goal cells after N steps
+    p_lava: np.ndarray | None = None           # mass on lava cells (absorbed; under lava="nodeath" standing there)
+    p_alive: np.ndarray | None = None          # mass still on empty / floor cells
+    expected_return: np.ndarray | None = None  # sum of ret = <mu_0, V_0^pi>
+    expected_steps: np.ndarray | None = None   # sum of occ: the expected number of steps taken (for gamma = 1)
+
+
+def occupancy_masks(cells: np.ndarray) -> dict:
+    """(B, S) masks of the XYD states standing on goal, lava and empty / floor cells of (B, H, W) cell codes."""
+    flat = np.asarray(cells).reshape(cells.shape[0], -1)
+    goal, lava = flat == OBJECT_TO_IDX["goal"], flat == OBJECT_TO_IDX["lava"]
+    free = (flat == OBJECT_TO_IDX["empty"]) | (flat == OBJECT_TO_IDX["floor"])
+    return {k: np.repeat(m, 4, axis=1) for k, m in (("goal", goal), ("lava", lava), ("alive", free))}
+
+
+def occupancy_derived(cells: np.ndarray, mu: np.ndarray, occ: np.ndarray, ret: np.ndarray) -> dict:
+    """p_goal, p_lava, p_alive, expected_return, expected_steps per grid: float64 sums of the planes."""
+    m = occupancy_masks(cells)
+    B = mu.shape[0]
+
+    def total(plane, mask=None):
+        return np.array([np.sum(plane[b] if mask is None else plane[b][mask[b]], dtype=np.float64) for b in range(B)])
+
+    return {"p_goal": total(mu, m["goal"]), "p_lava": total(mu, m["lava"]), "p_alive": total(mu, m["alive"]),
+            "expected_return": total(ret), "expected_steps": total(occ)}
+
+
 # Handles still open at interpreter exit are destroyed explicitly: a lone-grid handle may keep a
 # persistent solver resident on its stream, and destroy() asks it to leave and drains the stream.
 _LIVE: "weakref.WeakSet[ValueIteration]" = weakref.WeakSet()
@@ -230,6 +270,7 @@ class ValueIteration:
         cells = np.ascontiguousarray(cells, np.uint8)
         _lib.check(self.L.mgdp_vi_load_cells(self.h, _lib.ptr(cells)), "mgdp_vi_load_cells")
         self._cells_digest = hashlib.sha256(cells.tobytes()).hexdigest()  # checkpoint() / resume()
+        self._cells = cells  # occupancy(): the masks of its derived sums
         self.sweeps = 0
         self.converged = False
         self.dv = float("nan")
@@ -245,6 +286,7 @@ class ValueIteration:
         if rc:
             _lib.check(rc, "mgdp_vi_load_cells_device")
         self._cells_digest = None  # not read back: a checkpoint of these grids cannot be verified
+        self._cells = None
         self.sweeps = 0
         self.converged = False
         self.dv = float("nan")
@@ -403,6 +445,75 @@ class ValueIteration:
         """policy_iteration() on a plain or lava="nodeath" handle (mgdp_vi_policy_iteration_opts); refused
         on a finite horizon (its greedy step is the solve itself)."""
         return self._call_policy_iteration("mgdp_vi_policy_iteration_opts", pi0, max_iters)
+
+    # -- the forward pass of a policy (DESIGN.md section 21)
+    def _occupancy_steps(self, n_steps) -> int:
+        if self.horizon > 0:
+            if n_steps is not None and int(n_steps) != self.horizon:
+                raise ValueError(f"n_steps = {n_steps} on a finite-horizon handle: None or the horizon {self.horizon}")
+            return self.horizon
+        if n_steps is None:
+            raise ValueError("n_steps is required on a horizon-0 handle")
+        return int(n_steps)
+
+    def _occupancy_policy(self, pi, N: int) -> tuple[np.ndarray, int]:
+        a = np.asarray(pi)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
+        if a.shape == (self.B, self.S):
+            T = 1
+        elif a.shape == (N, self.B, self.S):
+            T = N
+        else:
+            raise ValueError(f"policy of shape {a.shape} does not match {(self.B, self.S)} or {(N, self.B, self.S)}"
+                             f" (rows T = {a.shape[0] if a.ndim == 3 else '?'})")
+        if a.dtype != np.int8:
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError("policy entries do not fit int8 action lanes")
+            a = a.astype(np.int8)
+        return np.ascontiguousarray(a), T
+
+    def occupancy(self, pi, start, n_steps: int | None = None, every_step: bool = False) -> OccupancyResult:
+        """The forward pass mu_{t+1} = P_pi^T mu_t of a policy (mgdp_vi_occupancy): exactly N steps, N the
+        horizon on a finite-horizon handle and n_steps otherwise.  pi is (B, S) or (N, B, S) int8 lanes (row t
+        applies at step_count t: policy_t()'s and rollout()'s layout); start is (B,) state indices (one-hot)
+        or a (B, S) distribution mu_0.  XYD handles of W*H <= 1024 under any options; it reads the cells and
+        the options only, so it works before solve() and changes nothing a later solve() sees.  ValueError:
+        a lane outside [0, 7) on a valid state (naming grid, the smallest such t, and state), a start index out
+        of range or on a wall / goal / terminal lava, mu_0 mass on one of those, rows other than 1 or N, a
+        DoorKey handle.  every_step=True also returns every mu_t as (N, B, S)."""
+        N = self._occupancy_steps(n_steps)
+        a, T = self._occupancy_policy(pi, N)
+        st = np.asarray(start)
+        s_idx = mu0 = None
+        if st.shape == (self.B,) and st.dtype.kind in "iu":
+            s_idx = np.ascontiguousarray(np.clip(st.astype(np.int64), -1, 2 ** 31 - 1), np.int32)
+        elif st.shape == (self.B, self.S):
+            mu0 = np.ascontiguousarray(st, self.np_dtype)
+        else:
+            raise ValueError(f"start of shape {st.shape} is neither {(self.B,)} state indices nor a {(self.B, self.S)} array")
+        mu, occ, ret = (np.empty((self.B, self.S), self.np_dtype) for _ in range(3))
+        mu_t = np.empty((N, self.B, self.S), self.np_dtype) if every_step else None
+        _lib.check(self.L.mgdp_vi_occupancy(self.h, _lib.ptr(a), T, _lib.ptr(s_idx), _lib.ptr(mu0), N, _lib.ptr(mu),
+                                            _lib.ptr(occ), _lib.ptr(ret), _lib.ptr(mu_t)), "mgdp_vi_occupancy")
+        cells = getattr(self, "_cells", None)
+        derived = occupancy_derived(cells, mu, occ, ret) if cells is not None else {}
+        return OccupancyResult(mu, occ, ret, mu_t, N, self.model, self.W, self.H, **derived)
+
+    def occupancy_device(self, pi_ptr: int, T: int, mu_ptr: int, start_ptr: int | None = None, mu0_ptr: int | None = None,
+                         n_steps: int | None = None, occ_ptr: int | None = None, ret_ptr: int | None = None,
+                         mu_t_ptr: int | None = None) -> int:
+        """occupancy() on device memory (mgdp_vi_occupancy_device), on the handle's stream: the policy (T*B*S
+        int8, T = 1 or N), start (B int32) or mu0 (B*S), and the outputs mu (required), occ, ret (B*S) and
+        mu_t (N*B*S) of the handle's dtype, 16-byte aligned (start: 4).  Returns N; the results are complete."""
+        N = self._occupancy_steps(n_steps)
+
+        def p(x):
+            return None if x is None else ctypes.c_void_p(int(x))
+
+        _lib.check(self.L.mgdp_vi_occupancy_device(self.h, p(pi_ptr), int(T), p(start_ptr), p(mu0_ptr), N, p(mu_ptr),
+                                                   p(occ_ptr), p(ret_ptr), p(mu_t_ptr)), "mgdp_vi_occupancy_device")
+        return N
 
     # sweeps / dv / converged of the last result: read from solve()'s outputs while they are current
     def _result_attr(self, i, name):
@@ -682,6 +793,16 @@ def policy_evaluation(grids, pi, **kwargs) -> VIResult:
         else:
             vi.evaluate(pi)
         return vi.result()
+    finally:
+        vi.close()
+
+
+def policy_occupancy(grids, pi, start, n_steps: int | None = None, every_step: bool = False, **kwargs) -> OccupancyResult:
+    """The forward pass of one policy per grid (ValueIteration.occupancy) on one GPU; kwargs as
+    ValueIteration (gamma, slip_p, lava, death_cost, horizon, dtype, ...)."""
+    vi = ValueIteration(grids, **kwargs)
+    try:
+        return vi.occupancy(pi, start, n_steps=n_steps, every_step=every_step)
     finally:
         vi.close()
 
