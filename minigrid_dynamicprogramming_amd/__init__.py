@@ -2,7 +2,8 @@
 
 Hot path (HIP, gfx950, libmgdp.so behind include/mgdp.h):
   * MiniGridEnv.step / gen_obs for batches of envs            (csrc/envs.hip)
-  * Jacobi value iteration over (pos, dir[, has_key, door_open]) (csrc/vi.hip)
+  * Jacobi value iteration over (pos, dir[, has_key, door_open]) (csrc/vi.hip: the C ABI over the
+    host pieces csrc/vi_host*.h and the global stopping rule csrc/vi_rule.h)
   * policy evaluation (V^pi of a given policy), greedy improvement and policy iteration on the
     same model and stopping rule                              (csrc/vi_eval.h)
   * the same under NoDeath lava and finite horizons: V_0 and every V_t of a stationary or
