@@ -353,6 +353,27 @@ int mgdp_vi_occupancy(mgdp_vi *vi, const int8_t *pi, int32_t T, const int32_t *s
 int mgdp_vi_occupancy_device(mgdp_vi *vi, const int8_t *d_pi, int32_t T, const int32_t *d_start, const void *d_mu0,
                              int32_t n_steps, void *d_mu, void *d_occ, void *d_ret, void *d_mu_t);
 
+/* Action values (additive entry points, the ABI version is unchanged): Q(s,a) of the
+ * handle's current V -- Q* after a solve, Q^pi after an evaluation -- and the set of maximising actions per
+ * state, in one pass per grid.  The values are bit for bit the ones mgdp_vi_improve compares:
+ *     Qd[s,a] = done ? R : fl(R + fl(gamma * V[s']))     (NoDeath lava: the move into lava carries death_cost)
+ *     Q[s,a]  = Qd[s,a], or under slip fl(fl(p * Qd[s,a]) + fl(c * s6)), s6 = ((((Qd0+Qd1)+Qd2)+Qd3)+Qd4)+Qd5
+ *   Q:   [B][S][A] of the handle's dtype, row-major; A = 7 (XYD; lanes 3..6 hold the same bits) or 5 (DoorKey:
+ *        left, right, forward, pickup, toggle) -- the table layout of mgdp_envs_q_learn.  Walls and absorbing
+ *        states hold +0 in every lane.
+ *   opt: [B][S] uint8, bit a set iff Q[s,a] equals the largest of the state's lanes (equality in the handle's
+ *        dtype); 0 on walls and absorbing states.
+ *   Either output may be NULL; both NULL is MGDP_E_INVALID.  The handles mgdp_vi_improve_opts admits (fused
+ *   method, horizon 0, any size they hold); a finite horizon is MGDP_E_UNSUPPORTED (Q_t needs V_{t+1}, which
+ *   the handle does not keep); before any solve or evaluation MGDP_E_INVALID.  The call writes its outputs
+ *   only: V, pi, the per-grid sweeps, the protocol state and the dispatch order stay as they are, and a later
+ *   mgdp_vi_solve is the one it would have been.  mgdp_vi_kernel_time counts the launch.
+ *   mgdp_vi_action_values: host pointers, through device staging allocated at the first call that needs it.
+ *   mgdp_vi_action_values_device: device pointers (16-byte aligned), on the handle's stream; the results are
+ *     complete when it returns. */
+int mgdp_vi_action_values(mgdp_vi *vi, void *Q, uint8_t *opt);
+int mgdp_vi_action_values_device(mgdp_vi *vi, void *d_Q, uint8_t *d_opt);
+
 /* Results (host).  V: B*S of float or double per dtype; pi: B*S int8 (-1 = absorbing state). */
 int mgdp_vi_get_values(mgdp_vi *vi, void *V);
 int mgdp_vi_get_policy(mgdp_vi *vi, int8_t *pi);

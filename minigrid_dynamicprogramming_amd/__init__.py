@@ -10,6 +10,8 @@ Hot path (HIP, gfx950, libmgdp.so behind include/mgdp.h):
     time-indexed policy in exactly H sweeps                   (csrc/vi_eval_opts.h)
   * the forward pass of a policy on the same options: state distribution, absorbed mass,
     discounted visitation and reward in exactly N steps       (csrc/vi_occupancy.h)
+  * the action values Q(s, a) of a handle's V and the set of maximising actions per state, in
+    q_learn's table layout                                    (csrc/vi_qvalues.h)
   * tabular policies executed on resident envs: policy lookup and the fused rollout, many steps
     of every env in one launch                                (csrc/envs_rollout.h)
 Host side (this package): the reference's env API, registry and grid generators, the DP front end
@@ -20,8 +22,8 @@ from .core import (COLOR_NAMES, COLOR_TO_IDX, DIR_TO_VEC, IDX_TO_COLOR, IDX_TO_O
 from .minigrid_env import MiniGridEnv, MissionSpace
 from .envs import CrossingEnv, DistShiftEnv, DoorKeyEnv, EmptyEnv, FourRoomsEnv, LavaGapEnv
 from .registry import EnvSpec, make, register, registry
-from .dp import (OccupancyResult, ValueIteration, VIResult, policy_evaluation, policy_iteration, policy_occupancy,
-                 value_iteration)
+from .dp import (ActionValues, OccupancyResult, ValueIteration, VIResult, action_values, policy_evaluation,
+                 policy_iteration, policy_occupancy, value_iteration)
 from .vector import MiniGridVecEnv, QLearnResult, RolloutResult
 
 __version__ = "0.1.0"

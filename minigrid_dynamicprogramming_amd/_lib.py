@@ -91,6 +91,8 @@ SIGNATURES = {
     "mgdp_vi_policy_iteration_opts": (ctypes.c_int, [_P, _P, _I32, _I32P, _I64P, _I64P, _DP]),
     "mgdp_vi_occupancy": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "mgdp_vi_occupancy_device": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "mgdp_vi_action_values": (ctypes.c_int, [_P, _P, _P]),
+    "mgdp_vi_action_values_device": (ctypes.c_int, [_P, _P, _P]),
     "mgdp_vi_reset": (ctypes.c_int, [_P]),
     "mgdp_vi_run_local": (ctypes.c_int, [_P, _I32P]),
     "mgdp_vi_run_to": (ctypes.c_int, [_P, _I32, _DP]),

@@ -31,10 +31,13 @@
 //                     form).
 //   vi_occupancy_kernel (vi_occupancy.h)  the forward pass of a policy on the same options: state
 //                     distribution, absorbed mass, discounted visitation and reward.
+//   vi_qvalues_kernel (vi_qvalues.h)  the action values Q[B][S][A] of the handle's V and the set of maximising
+//                     actions per state, one pass per grid.
 // Device code is split into vi_model.h (model), vi_loops.h (workgroup loops), vi_kernels.h
 // (kernels); the host side into vi_host.h (the handle), vi_host_launch.h (launches, the plan's kernel
 // pointers), vi_host_serve.h (waits, resident servers, the solve's closing steps), vi_host_order.h
-// (dispatch order), vi_host_eval.h and vi_host_occupancy.h (those host paths); this file holds the C ABI.
+// (dispatch order), vi_host_eval.h, vi_host_occupancy.h and vi_host_qvalues.h (those host paths); this file
+// holds the C ABI.
 // Which loop a handle runs is decided once, in vi_plan.h (host-plain: plan_vi); vi_rule.h (host-plain)
 // is the global stopping rule that closes every solve and evaluation; vi_layout.h holds the LDS sizes
 // host and device share.
@@ -66,6 +69,7 @@
 #include "vi_eval.h"
 #include "vi_eval_opts.h"
 #include "vi_occupancy.h"
+#include "vi_qvalues.h"
 
 // ================================================================================================
 // Host side
@@ -78,6 +82,7 @@ using namespace mgdp;
 #include "vi_host_order.h"
 #include "vi_host_eval.h"
 #include "vi_host_occupancy.h"
+#include "vi_host_qvalues.h"
 
 extern "C" {
 
@@ -242,6 +247,7 @@ int mgdp_vi_destroy(mgdp_vi *vi) {
                     (void *)vi->d_pi_stage, vi->d_vt_stage, (void *)vi->d_occ_err, vi->d_occ_tab})
         (void)hipFree(p);  // every device buffer of the handle (null where never allocated)
     for (void *p : vi->d_occ_stage) (void)hipFree(p);
+    for (void *p : vi->d_q_stage) (void)hipFree(p);
     if (vi->h_out) (void)hipHostFree(vi->h_out);
     if (vi->h_stage) (void)hipHostFree(vi->h_stage);
     if (vi->own_stream) (void)hipStreamDestroy(vi->stream);
@@ -670,6 +676,16 @@ int mgdp_vi_occupancy(mgdp_vi *vi, const int8_t *pi, int32_t T, const int32_t *s
                       void *mu, void *occ, void *ret, void *mu_t) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
     return occupancy_host(vi, pi, T, start, mu0, n_steps, mu, occ, ret, mu_t);
+}
+
+int mgdp_vi_action_values_device(mgdp_vi *vi, void *d_Q, uint8_t *d_opt) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    return action_values_device(vi, d_Q, d_opt);
+}
+
+int mgdp_vi_action_values(mgdp_vi *vi, void *Q, uint8_t *opt) {
+    MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
+    return action_values_host(vi, Q, opt);
 }
 
 int mgdp_vi_solve_last(mgdp_vi *vi, int32_t *sweeps_out, double *dv_out, int32_t *converged_out) {

@@ -3,7 +3,7 @@
 // of departed servers, the epoch of a host-published launch, and the check of a cells array against the
 // model.  Part of the single translation unit vi.hip: included after the device headers, first of the
 // host pieces (vi_host.h, vi_host_launch.h, vi_host_serve.h, vi_host_order.h, vi_host_eval.h,
-// vi_host_occupancy.h, in this order).
+// vi_host_occupancy.h, vi_host_qvalues.h, in this order).
 #pragma once
 
 // The kernels a plan names (resolve_kernels), type-erased: the fused own-rule and run-to launches
@@ -103,6 +103,9 @@ struct mgdp_vi {
     int occ_tab_n = 0;
     void *d_occ_stage[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t occ_stage_cap[4] = {0, 0, 0, 0};
+    // mgdp_vi_action_values (vi_qvalues.h): device staging of the host form's Q and opt, grown the same way
+    void *d_q_stage[2] = {nullptr, nullptr};
+    size_t q_stage_cap[2] = {0, 0};
 };
 
 namespace {

@@ -3,9 +3,9 @@
 // the plain ABI names are its strict form (no option handle, T = 1, no V_t), the *_opts names check T / V_t and
 // take any handle.  An evaluation is the solve's protocol on vi_eval_kernel: every grid to its own stop, the
 // grids that stopped with dV != 0 to K = max k_e, then the global rule sweep by sweep if dV(K) >= tol
-// (vi_rule.h); on a finite horizon it is one launch of exactly H sweeps.  Also here: the timed launch on
-// eval_shape that vi_host_occupancy.h shares.  Part of the single translation unit vi.hip: included after
-// vi_host_order.h.
+// (vi_rule.h); on a finite horizon it is one launch of exactly H sweeps.  Also here: the timed launch of one
+// workgroup per grid that vi_host_occupancy.h (on eval_shape) and vi_host_qvalues.h (on its own shape) share.
+// Part of the single translation unit vi.hip: included after vi_host_order.h.
 #pragma once
 
 namespace {
@@ -63,17 +63,22 @@ int eval_buffers(mgdp_vi *vi) {
     return 0;
 }
 
-// A kernel of one workgroup per grid on eval_shape (the evaluation kernels, the occupancy kernel), timed: the
-// LDS limit raised above 64 KiB, an event pair, the launch with eval_geo as its first argument and `args`
-// behind it.  The caller reads the launch error.
+// A kernel of one workgroup per grid, timed: the LDS limit raised above 64 KiB, an event pair, the launch with
+// eval_geo as its first argument and `args` behind it.  The caller reads the launch error.
+template <typename K, typename... Args>
+int launch_per_grid(mgdp_vi *vi, K kern, int block, int lds, Args... args) {
+    const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
+    if (lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    TimedPair tp;
+    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(block), lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s), args...);
+    return 0;
+}
+// ... on eval_shape's block and LDS (the evaluation kernels, the occupancy kernel)
 template <typename K, typename... Args>
 int launch_on_eval_shape(mgdp_vi *vi, K kern, Args... args) {
     const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
-    if (s.lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
-    TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
-    hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(s.block), s.lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s), args...);
-    return 0;
+    return launch_per_grid(vi, kern, s.block, s.lds, args...);
 }
 
 // The launch of an evaluation kernel (vi_eval_kernel, vi_eval_nd_kernel, vi_eval_fh_kernel): the arguments

@@ -138,6 +138,22 @@ class OccupancyResult:
     expected_steps: np.ndarray | None = None   # sum of occ: the expected number of steps taken (for gamma = 1)
 
 
+@dataclass
+class ActionValues:
+    """The action values of a value function (dp.action_values)."""
+    Q: np.ndarray        # (B, S, A) in the handle's dtype, +0 on walls and absorbing states
+    opt: np.ndarray      # (B, S) uint8, bit a: Q[s, a] is the state's maximum; 0 on walls and absorbing states
+    V: np.ndarray        # (B, S) the value function Q was read from (V*, or V^pi of the given policy)
+    pi: np.ndarray       # (B, S) int8: pi*, or the evaluated policy (-1 = absorbing)
+    sweeps: int
+    model: str
+
+    def advantage(self) -> np.ndarray:
+        """Q - V[..., None] on valid states, +0 elsewhere."""
+        valid = (self.opt != 0)[..., None]
+        return np.where(valid, self.Q - self.V[..., None], self.Q.dtype.type(0))
+
+
 def occupancy_masks(cells: np.ndarray) -> dict:
     """(B, S) masks of the XYD states standing on goal, lava and empty / floor cells of (B, H, W) cell codes."""
     flat = np.asarray(cells).reshape(cells.shape[0], -1)
@@ -515,6 +531,46 @@ class ValueIteration:
                                                    p(occ_ptr), p(ret_ptr), p(mu_t_ptr)), "mgdp_vi_occupancy_device")
         return N
 
+    # -- action values of the handle's V
+    def action_values(self, optimal: bool = False):
+        """Q(s, a) of the handle's current V (mgdp_vi_action_values): (B, S, A) in the handle's dtype -- Q* after
+        solve(), Q^pi after evaluate(pi) -- bit for bit the values improve() compares; +0 on walls and absorbing
+        states.  A = n_actions(model): XYD 7 (lanes 3..6 hold the same bits), DoorKey 5; the layout is
+        MiniGridVecEnv.q_learn's, so an fp64 handle's table passes to q_learn(Q=...), q_greedy and rollout as it
+        is.  optimal=True returns (Q, opt), opt as optimal_actions().  The handles improve_opts() admits; ValueError
+        on a finite horizon and before any solve or evaluation.  Nothing of the handle changes."""
+        Q = np.empty((self.B, self.S, n_actions(self.model)), self.np_dtype)
+        opt = np.empty((self.B, self.S), np.uint8) if optimal else None
+        _lib.check(self.L.mgdp_vi_action_values(self.h, _lib.ptr(Q), _lib.ptr(opt)), "mgdp_vi_action_values")
+        return (Q, opt) if optimal else Q
+
+    def optimal_actions(self) -> np.ndarray:
+        """(B, S) uint8: bit a is set iff Q(s, a) equals max_a' Q(s, a') in the handle's dtype; 0 on walls and
+        absorbing states.  The opt-only launch: no Q is allocated or written."""
+        opt = np.empty((self.B, self.S), np.uint8)
+        _lib.check(self.L.mgdp_vi_action_values(self.h, None, _lib.ptr(opt)), "mgdp_vi_action_values")
+        return opt
+
+    def action_values_device(self, q_ptr: int | None, opt_ptr: int | None = None) -> None:
+        """action_values() into device memory (mgdp_vi_action_values_device), on the handle's stream: Q (B*S*A of
+        the handle's dtype) at q_ptr and / or opt (B*S uint8) at opt_ptr, 16-byte aligned (e.g. torch tensors'
+        data_ptr()); either may be None, not both.  The results are complete when it returns."""
+        def p(x):
+            return None if x is None else ctypes.c_void_p(int(x))
+
+        _lib.check(self.L.mgdp_vi_action_values_device(self.h, p(q_ptr), p(opt_ptr)), "mgdp_vi_action_values_device")
+
+    def is_optimal(self, pi) -> np.ndarray:
+        """(B, S) bool: whether pi's lane is a maximising action of the handle's V, whichever it chose among ties;
+        True on walls and absorbing states (whatever their entry), False where a valid state's lane is outside
+        [0, A).  pi as evaluate() takes it."""
+        a = self._check_policy(pi)
+        opt = self.optimal_actions()
+        lane = a.astype(np.int64)
+        inr = (lane >= 0) & (lane < n_actions(self.model))
+        hit = ((opt.astype(np.int64) >> np.where(inr, lane, 0)) & 1).astype(bool) & inr
+        return hit | (opt == 0)
+
     # sweeps / dv / converged of the last result: read from solve()'s outputs while they are current
     def _result_attr(self, i, name):
         live = self.__dict__.get("_live")
@@ -803,6 +859,23 @@ def policy_occupancy(grids, pi, start, n_steps: int | None = None, every_step: b
     vi = ValueIteration(grids, **kwargs)
     try:
         return vi.occupancy(pi, start, n_steps=n_steps, every_step=every_step)
+    finally:
+        vi.close()
+
+
+def action_values(grids, pi=None, **kwargs) -> ActionValues:
+    """Q*, or Q^pi of one policy per grid ((B, S) int8, see ValueIteration.evaluate), with the optimal-action
+    sets, on one GPU; kwargs as ValueIteration (gamma, tol, slip_p, lava, dtype, ...)."""
+    vi = ValueIteration(grids, **kwargs)
+    try:
+        if pi is None:
+            vi.solve()
+        elif _has_options(kwargs):
+            vi.evaluate_opts(pi)
+        else:
+            vi.evaluate(pi)
+        Q, opt = vi.action_values(optimal=True)
+        return ActionValues(Q, opt, vi.values(), vi.policy(), vi.sweeps, vi.model)
     finally:
         vi.close()
 
