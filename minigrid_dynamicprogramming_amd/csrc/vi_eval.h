@@ -1,9 +1,9 @@
 // vi_eval.h -- policy evaluation and greedy improvement: V^pi of a given
 // policy by Jacobi sweeps under the stopping rule of the solve, and pi' = argmax_a Q on the handle's V.
-// Part of the single translation unit vi.hip (included after vi_kernels.h).  The steps are the
-// per-action forms of xyd_step / dk_step (vi_model.h) with Q[pi(s)] in place of the max over
-// actions: same operands in the same order, so every Q is bit-identical to the table form
-// Qd = done ? R : fl(R + g*V[s']) of the oracle's tables.
+// Part of the single translation unit vi.hip (included after vi_kernels.h).  The steps take the
+// per-action values from vi_model.h's one statement of them (xyd_forward, xyd_slip_tail / xyd_mix,
+// dk_reads / dk_forward / dk_q5, q_argmax) with Q[pi(s)] in place of the max over actions, so every
+// Q is bit-identical to the table form Qd = done ? R : fl(R + g*V[s']) of the oracle's tables.
 #pragma once
 
 namespace mgdp {
@@ -40,7 +40,7 @@ template <> struct PkOf<MGDP_MODEL_DOORKEY> { using type = Pk16; };
 // ------------------------------------------------------------------------------------------------
 // The evaluation step of one cell: V'[s] = Q[s, pi(s)].  Deterministic: the value the chosen action
 // reads is selected first, then multiplied once (fl(g * x), the table's R = 0 form); a terminal
-// forward move takes its constant.  Slip: the six-term chain of xyd_step, exactly as written there.
+// forward move takes its constant.  Slip: fl(p*Qd[pi(s)]) + xyd_slip_tail, the six-term chain.
 // An absorbing state's lane is -1 (0xff): it falls to the self loop and is then zeroed.
 // ------------------------------------------------------------------------------------------------
 template <typename T, bool SLIP>
@@ -66,15 +66,9 @@ __device__ __forceinline__ T xyd_eval_step(const XydTopo<T> &tp, const Coef<T> &
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const uint32_t a = (pk >> (8 * d)) & 0xffu;
-        const T qM = cf.g * nbv[d];
-        const T qF = ((tp.term >> d) & 1u) ? tp.tq[d] : qM;
+        const T qF = xyd_forward<T, false, false>(tp, cf, d, nbv[d], (T)1);
         const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T s6 = qL + qR;
-        s6 = s6 + qF;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        const T tail = cf.c * s6;
+        const T tail = xyd_slip_tail(cf, qL, qR, qF, qS);
         const T qa = a == 0u ? qL : (a == 1u ? qR : (a == 2u ? qF : qS));
         T best = cf.p * qa + tail;
         best = tp.valid ? best : (T)0;  // slip mixes in constants; absorbing states stay 0
@@ -92,7 +86,6 @@ __device__ __forceinline__ T dk_eval_step(const DkTopo &tp, const Coef<T> &cf, c
     for (int d = 0; d < 4; ++d) {
         const uint32_t f = tp.f[d];
         const V4<T> &nb = nbs[d];
-        const bool goal = f & 16u, lava = f & 32u, key = f & 64u, door = f & 128u;
 #pragma unroll
         for (int hk = 0; hk < 2; ++hk) {
 #pragma unroll
@@ -101,15 +94,13 @@ __device__ __forceinline__ T dk_eval_step(const DkTopo &tp, const Coef<T> &cf, c
                 const int hd = hk * 2 + dop;
                 const uint32_t a = (pk.w[l >> 2] >> (8 * (l & 3))) & 0xffu;
                 const T xS = own[l];
-                const T xL = own[(((d + 3) & 3) * 2 + hk) * 2 + dop];
-                const T xR = own[(((d + 1) & 3) * 2 + hk) * 2 + dop];
-                const T xM = ((f >> hd) & 1u) ? nb.v[hd] : xS;
-                const T xP = (!hk && key) ? own[(d * 2 + 1) * 2 + dop] : xS;
-                const T xD = dop ? own[(d * 2 + hk) * 2 + 0] : (hk ? own[(d * 2 + hk) * 2 + 1] : xS);
-                const T xT = door ? xD : xS;
+                const T xL = own[((d + 3) & 3) * 4 + hd];
+                const T xR = own[((d + 1) & 3) * 4 + hd];
+                T xM, xP, xT;
+                dk_reads(f, hk, dop, own + d * 4, nb.v[hd], xM, xP, xT);
                 const T x = a == 0u ? xL : (a == 1u ? xR : (a == 2u ? xM : (a == 3u ? xP : (a == 4u ? xT : xS))));
                 T q = cf.g * x;
-                if (a == 2u) q = goal ? (T)1 : (lava ? (T)0 : q);
+                if (a == 2u) q = dk_forward<T, false>(f, q, (T)1);
                 const T best = ((tp.walk >> hd) & 1u) ? q : (T)0;
                 outv[l] = best;
                 dv = vmax(dv, vabs(best - own[l]));
@@ -333,7 +324,7 @@ vi_eval_kernel(Geo geo, Coef<T> cf, const uint8_t *__restrict__ cells, T *__rest
 // ------------------------------------------------------------------------------------------------
 // Greedy improvement: pi'(s) = argmax_a Q(s, a) on V, lowest action index among exact maxima, except
 // that pi(s) stays when Q(s, pi(s)) equals the maximum (so "no state changed" is a valid stop of policy
-// iteration).  Q is the per-action form of xyd_step / dk_step (slip: p*Qd[a] + tail).  Returns the
+// iteration).  Q is xyd_mix / dk_q5 (vi_model.h), the values xyd_step / dk_step maximise.  Returns the
 // packed new lanes and adds the changed valid states to n.  A current lane outside [0, A) never keeps.
 // ND: the NoDeath Q -- the move into lava carries dc; Q may be negative, and the
 // comparisons are plain either way.
@@ -347,30 +338,12 @@ __device__ __forceinline__ uint32_t xyd_improve_step(const XydTopo<T> &tp, const
     uint32_t pk = 0;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        T qM = cf.g * nbv[d];
-        if constexpr (ND) qM = ((tp.lavaF >> d) & 1u) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
-        const T qF = ((tp.term >> d) & 1u) ? tp.tq[d] : qM;
-        const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T a0 = qL, a1 = qR, a2 = qF, a3 = qS;  // Q of actions 0..3 (4..6 equal action 3)
-        if (SLIP) {
-            T s6 = qL + qR;
-            s6 = s6 + qF;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            const T tail = cf.c * s6;
-            a0 = cf.p * qL + tail;
-            a1 = cf.p * qR + tail;
-            a2 = cf.p * qF + tail;
-            a3 = cf.p * qS + tail;
-        }
-        uint32_t arg = 0;
-        T best = a0;
-        if (a1 > best) { best = a1; arg = 1; }
-        if (a2 > best) { best = a2; arg = 2; }
-        if (a3 > best) { best = a3; arg = 3; }
+        T q[4];
+        xyd_mix<T, SLIP>(cf, gv[(d + 3) & 3], gv[(d + 1) & 3], xyd_forward<T, ND, false>(tp, cf, d, nbv[d], (T)1), gv[d], q);
+        uint32_t arg;
+        const T best = q_argmax(q, arg);
         const uint32_t cur = (old >> (8 * d)) & 0xffu;
-        const T qc = cur == 0u ? a0 : (cur == 1u ? a1 : (cur == 2u ? a2 : a3));
+        const T qc = cur == 0u ? q[0] : (cur == 1u ? q[1] : (cur == 2u ? q[2] : q[3]));
         if (cur < 7u && qc == best) arg = cur;
         if (tp.valid && arg != cur) ++n;
         pk |= (tp.valid ? arg : 0xffu) << (8 * d);
@@ -389,30 +362,19 @@ __device__ __forceinline__ Pk16 dk_improve_step(const DkTopo &tp, const Coef<T> 
     for (int d = 0; d < 4; ++d) {
         const uint32_t f = tp.f[d];
         const V4<T> &nb = nbs[d];
-        const bool goal = f & 16u, lava = f & 32u, key = f & 64u, door = f & 128u;
 #pragma unroll
         for (int hk = 0; hk < 2; ++hk) {
 #pragma unroll
             for (int dop = 0; dop < 2; ++dop) {
                 const int l = (d * 2 + hk) * 2 + dop;
                 const int hd = hk * 2 + dop;
-                const T qS = gv[l];
-                const T qL = gv[(((d + 3) & 3) * 2 + hk) * 2 + dop];
-                const T qR = gv[(((d + 1) & 3) * 2 + hk) * 2 + dop];
-                const T qM = ((f >> hd) & 1u) ? cf.g * nb.v[hd] : qS;
-                const T qF = goal ? (T)1 : (lava ? (T)0 : qM);
-                const T qP = (!hk && key) ? gv[(d * 2 + 1) * 2 + dop] : qS;
-                const T qD = dop ? gv[(d * 2 + hk) * 2 + 0] : (hk ? gv[(d * 2 + hk) * 2 + 1] : qS);
-                const T qT = door ? qD : qS;
+                T q[5];
+                dk_q5(f, hk, dop, gv[((d + 3) & 3) * 4 + hd], gv[((d + 1) & 3) * 4 + hd], gv + d * 4, cf.g * nb.v[hd], q);
                 const bool valid = (tp.walk >> hd) & 1u;
-                T best = qL;
-                uint32_t arg = 0;
-                if (qR > best) { best = qR; arg = 1; }
-                if (qF > best) { best = qF; arg = 2; }
-                if (qP > best) { best = qP; arg = 3; }
-                if (qT > best) { best = qT; arg = 4; }
+                uint32_t arg;
+                const T best = q_argmax(q, arg);
                 const uint32_t cur = (old.w[l >> 2] >> (8 * (l & 3))) & 0xffu;
-                const T qc = cur == 0u ? qL : (cur == 1u ? qR : (cur == 2u ? qF : (cur == 3u ? qP : qT)));
+                const T qc = cur == 0u ? q[0] : (cur == 1u ? q[1] : (cur == 2u ? q[2] : (cur == 3u ? q[3] : q[4])));
                 if (cur < 5u && qc == best) arg = cur;
                 if (valid && arg != cur) ++n;
                 pk.w[l >> 2] |= (valid ? arg : 0xffu) << (8 * (l & 3));

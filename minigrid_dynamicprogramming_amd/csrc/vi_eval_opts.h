@@ -91,7 +91,7 @@ __device__ __forceinline__ void lanes_report(const PkN<MODEL> &pk, uint32_t vmas
 // ------------------------------------------------------------------------------------------------
 // The evaluation step of one XYD cell under the options: xyd_eval_step with the NoDeath lava move
 // (ND: fl(dc + fl(g*x)) for a forward move into lava -- the operand is still selected first and
-// multiplied once) and the finite-horizon goal reward (FH: rg in place of 1).  Slip: xyd_step's chain.
+// multiplied once) and the finite-horizon goal reward (FH: rg in place of 1).  Slip: xyd_slip_tail's chain.
 // ------------------------------------------------------------------------------------------------
 template <typename T, bool SLIP, bool ND, bool FH>
 __device__ __forceinline__ void xyd_eval_step_opts(const XydTopo<T> &tp, const Coef<T> &cf, const T (&own)[4],
@@ -122,15 +122,11 @@ __device__ __forceinline__ void xyd_eval_step_opts(const XydTopo<T> &tp, const C
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const uint32_t a = (pk >> (8 * d)) & 0xffu;
+        // (xyd_forward<T, ND, FH> restated: through it the slip NoDeath kernels changed their register assignment)
         const T qM = (ND && ((tp.lavaF >> d) & 1u)) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
         const T qF = ((tp.term >> d) & 1u) ? (FH ? tp.tq[d] * rg : tp.tq[d]) : qM;
         const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T s6 = qL + qR;
-        s6 = s6 + qF;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        const T tail = cf.c * s6;
+        const T tail = xyd_slip_tail(cf, qL, qR, qF, qS);
         T qa = qS;
         qa = a == 2u ? qF : qa;
         qa = a == 1u ? qR : qa;
@@ -148,7 +144,7 @@ __device__ __forceinline__ void dk_eval_step_fh(const DkTopo &tp, const Coef<T> 
     for (int d = 0; d < 4; ++d) {
         const uint32_t f = tp.f[d];
         const V4<T> &nb = nbs[d];
-        const bool goal = f & 16u, lava = f & 32u, key = f & 64u, door = f & 128u;
+        const bool goal = f & 16u, lava = f & 32u;
 #pragma unroll
         for (int hk = 0; hk < 2; ++hk) {
 #pragma unroll
@@ -157,12 +153,10 @@ __device__ __forceinline__ void dk_eval_step_fh(const DkTopo &tp, const Coef<T> 
                 const int hd = hk * 2 + dop;
                 const uint32_t a = (pk[l >> 2] >> (8 * (l & 3))) & 0xffu;
                 const T xS = own[l];
-                const T xL = own[(((d + 3) & 3) * 2 + hk) * 2 + dop];
-                const T xR = own[(((d + 1) & 3) * 2 + hk) * 2 + dop];
-                const T xM = ((f >> hd) & 1u) ? nb.v[hd] : xS;
-                const T xP = (!hk && key) ? own[(d * 2 + 1) * 2 + dop] : xS;
-                const T xD = dop ? own[(d * 2 + hk) * 2 + 0] : (hk ? own[(d * 2 + hk) * 2 + 1] : xS);
-                const T xT = door ? xD : xS;
+                const T xL = own[((d + 3) & 3) * 4 + hd];
+                const T xR = own[((d + 1) & 3) * 4 + hd];
+                T xM, xP, xT;
+                dk_reads(f, hk, dop, own + d * 4, nb.v[hd], xM, xP, xT);
                 T x = xS;
                 x = a == 4u ? xT : x;
                 x = a == 3u ? xP : x;
@@ -170,7 +164,7 @@ __device__ __forceinline__ void dk_eval_step_fh(const DkTopo &tp, const Coef<T> 
                 x = a == 1u ? xR : x;
                 x = a == 0u ? xL : x;
                 T q = cf.g * x;
-                const T qt = goal ? rg : (T)0;  // a terminal front: the goal's reward, lava's 0
+                const T qt = goal ? rg : (T)0;  // a terminal front: dk_forward<T, true> (vi_model.h) as one flat select
                 q = (a == 2u && (goal || lava)) ? qt : q;
                 outv[l] = ((tp.walk >> hd) & 1u) ? q : (T)0;
             }

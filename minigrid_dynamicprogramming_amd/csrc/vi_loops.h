@@ -2332,7 +2332,9 @@ __device__ __forceinline__ T dkh_step_fast(const DkHalf &tp, const Coef<T> &cf, 
     return dv;
 }
 
-// pi of one half (dk_step's WRITE_PI form restricted to has_key = hk): pk[d] = the 2 lanes' bytes
+// pi of one half (dk_step's WRITE_PI form restricted to has_key = hk): pk[d] = the 2 lanes' bytes.
+// Restates dk_q5 and q_argmax (vi_model.h) on the half layout -- the has_key sibling is the other
+// half's state, multiplied only where pickup reads it: through them the half loop's kernels moved.
 template <typename T>
 __device__ __forceinline__ void dkh_pi(const DkTopo &tp, const Coef<T> &cf, int hk, const T (&own)[8], const T (&oth)[8],
                                        const V2<T> (&nbs)[4], uint32_t (&pk)[4]) {
@@ -2604,26 +2606,6 @@ __device__ __forceinline__ Xyd2Topo<T> xyd2_topo(const uint8_t *cl, const Geo &g
     return t;
 }
 
-// Value of one XYD state from its four distinct action values (the WRITE_PI = false branch of
-// xyd_step, operation for operation).
-template <typename T, bool SLIP>
-__device__ __forceinline__ T xyd_value(const Coef<T> &cf, T qL, T qR, T qF, T qS) {
-    T a0 = qL, a1 = qR, a2 = qF, a3 = qS;
-    if (SLIP) {
-        T s6 = qL + qR;
-        s6 = s6 + qF;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        s6 = s6 + qS;
-        const T tail = cf.c * s6;
-        a0 = cf.p * qL + tail;
-        a1 = cf.p * qR + tail;
-        a2 = cf.p * qF + tail;
-        a3 = cf.p * qS + tail;
-    }
-    return vmax(vmax(a0, a1), vmax(a2, a3));
-}
-
 template <typename T, bool SLIP, bool LOCAL, typename Done>
 __device__ __forceinline__ void fused_fast_xyd2(const Geo &geo, const Coef<T> &cf, const uint8_t *cl,
                                                 T *vbase, int8_t *pis, T *slots, uint8_t *flags,
@@ -2783,24 +2765,16 @@ __device__ __forceinline__ void fused_quad_xyd(const Geo &geo, const Coef<T> &cf
         const T nb = Vp[nbi];
         const T vl = quad_perm<kQuadLeft>(vprev), vr = quad_perm<kQuadRight>(vprev);
         const T qL = cf.g * vl, qR = cf.g * vr, qS = cf.g * vprev, qF = term ? tq : cf.g * nb;
-        T a0 = qL, a1 = qR, a2 = qF, a3 = qS;
-        if (SLIP) {
-            T s6 = qL + qR;
-            s6 = s6 + qF;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            const T tail = cf.c * s6;
-            a0 = cf.p * qL + tail;
-            a1 = cf.p * qR + tail;
-            a2 = cf.p * qF + tail;
-            a3 = cf.p * qS + tail;
+        T q[4] = {qL, qR, qF, qS};
+        if (SLIP) {  // (xyd_mix restated around the shared chain: through it the slip kernel lost an instruction)
+            const T tail = xyd_slip_tail(cf, qL, qR, qF, qS);
+            q[0] = cf.p * qL + tail;
+            q[1] = cf.p * qR + tail;
+            q[2] = cf.p * qF + tail;
+            q[3] = cf.p * qS + tail;
         }
-        int arg = 0;
-        T best = a0;
-        if (a1 > best) { best = a1; arg = 1; }
-        if (a2 > best) { best = a2; arg = 2; }
-        if (a3 > best) { best = a3; arg = 3; }
+        int arg;
+        q_argmax(q, arg);
         if (own_cell) pis[s] = valid ? (int8_t)arg : (int8_t)-1;
     }
     __syncthreads();

@@ -194,8 +194,64 @@ __device__ __forceinline__ void xyd_load_nb(const XydTopo<T> &tp, const T *Vin, 
     for (int d = 0; d < 4; ++d) nbv[d] = Vin[tp.nbi[d]];
 }
 
+// ------------------------------------------------------------------------------------------------
+// The per-action value of a state, stated once: the rounding specification every solve, evaluation,
+// improvement and Q kernel is asserted against, bit for bit (DESIGN.md sections 13, 19, 22):
+//     Qd[s,a] = done ? R : fl(R + fl(g*V[s']))
+//     Q[s,a]  = Qd[s,a], or under slip fl(fl(p*Qd[s,a]) + fl(c*s6)), s6 the six-term sum left to right
+// The pieces here (XYD) and before dk_step (DoorKey) are its text.  Outside them stand sa_sweep (one
+// lane per action), the value-only forms (xyd_step / dk_step without WRITE_PI, dk_step_fast: an
+// equivalent formulation, proven there), and the few restatements that a kernel's machine code
+// forced; each carries a comment naming what it restates (DESIGN.md section 22 lists them).
+// ------------------------------------------------------------------------------------------------
+// Slip: fl(c*s6) of a state with the distinct action values left, right, forward, self (actions
+// 3..5 all take the self value).
+template <typename T>
+__device__ __forceinline__ T xyd_slip_tail(const Coef<T> &cf, T qL, T qR, T qF, T qS) {
+    T s6 = qL + qR;
+    s6 = s6 + qF;
+    s6 = s6 + qS;
+    s6 = s6 + qS;
+    s6 = s6 + qS;
+    return cf.c * s6;
+}
+// Q of actions 0..3 of an XYD state (4..6 equal action 3) from its deterministic values.
+template <typename T, bool SLIP>
+__device__ __forceinline__ void xyd_mix(const Coef<T> &cf, T qL, T qR, T qF, T qS, T (&q)[4]) {
+    q[0] = qL, q[1] = qR, q[2] = qF, q[3] = qS;
+    if (SLIP) {
+        const T tail = xyd_slip_tail(cf, qL, qR, qF, qS);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) q[a] = cf.p * q[a] + tail;
+    }
+}
+// Value of one XYD state from its four distinct action values.
+template <typename T, bool SLIP>
+__device__ __forceinline__ T xyd_value(const Coef<T> &cf, T qL, T qR, T qF, T qS) {
+    T q[4];
+    xyd_mix<T, SLIP>(cf, qL, qR, qF, qS, q);
+    return vmax(vmax(q[0], q[1]), vmax(q[2], q[3]));
+}
+// Deterministic value of forward from direction d; nb = the V forward reads (xyd_load_nb).
 // ND: NoDeath lava (entering it: Q = death_cost + g*V[lava state]); FH: finite horizon, the goal
 // reward of this sweep is rg (the exact _reward() of its step_count) instead of 1.
+template <typename T, bool ND, bool FH>
+__device__ __forceinline__ T xyd_forward(const XydTopo<T> &tp, const Coef<T> &cf, int d, T nb, T rg) {
+    const T qM = (ND && ((tp.lavaF >> d) & 1u)) ? cf.dc + cf.g * nb : cf.g * nb;
+    return ((tp.term >> d) & 1u) ? (FH ? tp.tq[d] * rg : tp.tq[d]) : qM;
+}
+// The maximum of q and, in arg, the lowest action index among its exact maxima (numpy's argmax rule).
+template <typename T, int N, typename I>
+__device__ __forceinline__ T q_argmax(const T (&q)[N], I &arg) {
+    T best = q[0];
+    I am = 0;  // (a local, stored once: updated through the reference, xyd_step's kernels came out differently)
+#pragma unroll
+    for (int a = 1; a < N; ++a)
+        if (q[a] > best) { best = q[a]; am = a; }
+    arg = am;
+    return best;
+}
+
 template <typename T, bool SLIP, bool WRITE_PI, bool ND = false, bool FH = false>
 __device__ __forceinline__ T xyd_step(const XydTopo<T> &tp, const Coef<T> &cf, const V4<T> &own,
                                       const T (&nbv)[4], V4<T> &out, uint32_t &pk, T rg = (T)1) {
@@ -233,32 +289,18 @@ __device__ __forceinline__ T xyd_step(const XydTopo<T> &tp, const Coef<T> &cf, c
     pk = 0;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
+        // (xyd_forward<T, ND, FH> restated: through it the finite-horizon option kernels grew)
         const T qM = (ND && ((tp.lavaF >> d) & 1u)) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
         const T qF = ((tp.term >> d) & 1u) ? (FH ? tp.tq[d] * rg : tp.tq[d]) : qM;
-        const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T a0 = qL, a1 = qR, a2 = qF, a3 = qS;  // Q of actions 0..3 (4..6 equal action 3)
-        if (SLIP) {
-            T s6 = qL + qR;
-            s6 = s6 + qF;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            const T tail = cf.c * s6;
-            a0 = cf.p * qL + tail;
-            a1 = cf.p * qR + tail;
-            a2 = cf.p * qF + tail;
-            a3 = cf.p * qS + tail;
-        }
         T best;
         if (WRITE_PI) {
-            int arg = 0;
-            best = a0;
-            if (a1 > best) { best = a1; arg = 1; }
-            if (a2 > best) { best = a2; arg = 2; }
-            if (a3 > best) { best = a3; arg = 3; }
+            T q[4];
+            xyd_mix<T, SLIP>(cf, gv[(d + 3) & 3], gv[(d + 1) & 3], qF, gv[d], q);
+            int arg;
+            best = q_argmax(q, arg);
             pk |= (uint32_t)(uint8_t)(tp.valid ? arg : -1) << (8 * d);
         } else {
-            best = vmax(vmax(a0, a1), vmax(a2, a3));
+            best = xyd_value<T, SLIP>(cf, gv[(d + 3) & 3], gv[(d + 1) & 3], qF, gv[d]);
         }
         best = tp.valid ? best : (T)0;  // slip mixes in constants; absorbing states stay 0
         out.v[d] = best;
@@ -308,6 +350,34 @@ template <typename T>
 __device__ __forceinline__ void dk_load_nb(const DkTopo &tp, const T *Vin, V4<T> (&nb)[4]) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) nb[d] = *reinterpret_cast<const V4<T> *>(Vin + tp.nb[d]);
+}
+
+// What forward, pickup and toggle read in state (d, hk, dop) of a cell with front bits f = DkTopo::f[d]:
+// the state's own value where the action changes nothing, else the front state's (qN), the has_key
+// sibling's (d, 1, dop), or the door's other position.  qD: the four values of direction d of the cell,
+// index has_key*2 + door_open.  Selects only: the same text serves g*V and V itself (the evaluation
+// steps select the operand, then multiply once).  A goal or lava ahead is dk_forward's, not decided here.
+template <typename T>
+__device__ __forceinline__ void dk_reads(uint32_t f, int hk, int dop, const T *qd, T qN, T &qM, T &qP, T &qT) {
+    const bool key = f & 64u, door = f & 128u;
+    const T qS = qd[hk * 2 + dop];
+    qM = ((f >> (hk * 2 + dop)) & 1u) ? qN : qS;
+    qP = (!hk && key) ? qd[2 + dop] : qS;
+    const T qD = dop ? qd[hk * 2] : (hk ? qd[3] : qS);
+    qT = door ? qD : qS;
+}
+// Forward's value: the goal's reward (FH: rg of this sweep in place of 1), terminal lava's 0, else qM.
+template <typename T, bool FH>
+__device__ __forceinline__ T dk_forward(uint32_t f, T qM, T rg) {
+    return (f & 16u) ? (FH ? rg : (T)1) : ((f & 32u) ? (T)0 : qM);
+}
+// The five action values (left, right, forward, pickup, toggle) of state (d, hk, dop) from g*V: gL / gR of
+// the left- and right-turned state, gN of the front state, gd as dk_reads' qd.
+template <typename T>
+__device__ __forceinline__ void dk_q5(uint32_t f, int hk, int dop, T gL, T gR, const T *gd, T gN, T (&q)[5]) {
+    T qM;
+    dk_reads(f, hk, dop, gd, gN, qM, q[3], q[4]);
+    q[0] = gL, q[1] = gR, q[2] = dk_forward<T, false>(f, qM, (T)1);
 }
 
 // FH: finite horizon, the goal reward of this sweep is rg instead of 1 (see xyd_step).
@@ -368,27 +438,17 @@ __device__ __forceinline__ T dk_step(const DkTopo &tp, const Coef<T> &cf, const 
             for (int dop = 0; dop < 2; ++dop) {
                 const int l = (d * 2 + hk) * 2 + dop;
                 const int hd = hk * 2 + dop;
+                // (dk_q5 / dk_forward<T, FH> restated: through them the solve kernels' code moved)
                 const T qS = gv[l];
-                const T qL = gv[(((d + 3) & 3) * 2 + hk) * 2 + dop];
-                const T qR = gv[(((d + 1) & 3) * 2 + hk) * 2 + dop];
                 const T qM = ((f >> hd) & 1u) ? cf.g * nb.v[hd] : qS;
                 const T qF = goal ? (FH ? rg : (T)1) : (lava ? (T)0 : qM);
                 const T qP = (!hk && key) ? gv[(d * 2 + 1) * 2 + dop] : qS;
                 const T qD = dop ? gv[(d * 2 + hk) * 2 + 0] : (hk ? gv[(d * 2 + hk) * 2 + 1] : qS);
-                const T qT = door ? qD : qS;
+                const T q[5] = {gv[((d + 3) & 3) * 4 + hd], gv[((d + 1) & 3) * 4 + hd], qF, qP, door ? qD : qS};
                 const bool valid = (tp.walk >> hd) & 1u;
-                T best;
-                if (WRITE_PI) {
-                    best = qL;
-                    int arg = 0;
-                    if (qR > best) { best = qR; arg = 1; }
-                    if (qF > best) { best = qF; arg = 2; }
-                    if (qP > best) { best = qP; arg = 3; }
-                    if (qT > best) { best = qT; arg = 4; }
-                    pk[l >> 2] |= (uint32_t)(uint8_t)(valid ? arg : -1) << (8 * (l & 3));
-                } else {
-                    best = vmax(vmax(vmax(qL, qR), vmax(qF, qP)), qT);
-                }
+                int arg;
+                T best = q_argmax(q, arg);
+                pk[l >> 2] |= (uint32_t)(uint8_t)(valid ? arg : -1) << (8 * (l & 3));
                 best = valid ? best : (T)0;
                 outv[l] = best;
                 dv = vmax(dv, vabs(best - own[l]));

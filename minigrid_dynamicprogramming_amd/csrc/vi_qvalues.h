@@ -1,7 +1,7 @@
 // vi_qvalues.h -- the action values of the handle's V: Q[B][S][A] and the set of
 // maximising actions per state, opt[B][S] (bit a: Q[s,a] equals the row's maximum in T).  One pass per grid
 // over the V in HBM, staged as vi_improve_kernel stages it; the values are the ones its argmax compares,
-// written a second time here so that vi_improve_kernel's code stays as it is:
+// from the same definitions (vi_model.h: xyd_forward / xyd_mix, dk_q5, q_argmax):
 //     Qd[s,a] = done ? R : fl(R + fl(g*V[s']))       (R = 0 where not done; NoDeath lava: R = dc)
 //     Q[s,a]  = Qd[s,a]                               deterministic
 //     Q[s,a]  = fl(fl(p*Qd[s,a]) + fl(c*s6))          slip, s6 = ((((Qd0+Qd1)+Qd2)+Qd3)+Qd4)+Qd5
@@ -41,7 +41,7 @@ inline int qvalues_lds(int model, int HW, int HWp, int S, int tsize, bool write_
 template <typename T>
 __device__ __forceinline__ uint32_t q_opt_bit(T q, T m, uint32_t bits) { return q == m ? bits : 0u; }
 
-// The 28 values and 4 opt bytes of an XYD cell, in xyd_improve_step's operations and order.
+// The 28 values and 4 opt bytes of an XYD cell: the values xyd_improve_step compares.
 template <typename T, bool SLIP, bool ND>
 __device__ __forceinline__ uint32_t xyd_q_step(const XydTopo<T> &tp, const Coef<T> &cf, const V4<T> &own,
                                                const T (&nbv)[4], T (&q)[28]) {
@@ -51,44 +51,20 @@ __device__ __forceinline__ uint32_t xyd_q_step(const XydTopo<T> &tp, const Coef<
     uint32_t opt = 0;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        T qM = cf.g * nbv[d];
-        if constexpr (ND) qM = ((tp.lavaF >> d) & 1u) ? cf.dc + cf.g * nbv[d] : cf.g * nbv[d];
-        const T qF = ((tp.term >> d) & 1u) ? tp.tq[d] : qM;
-        const T qL = gv[(d + 3) & 3], qR = gv[(d + 1) & 3], qS = gv[d];
-        T a0 = qL, a1 = qR, a2 = qF, a3 = qS;  // Q of actions 0..3 (4..6 equal action 3)
-        if (SLIP) {
-            T s6 = qL + qR;
-            s6 = s6 + qF;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            s6 = s6 + qS;
-            const T tail = cf.c * s6;
-            a0 = cf.p * qL + tail;
-            a1 = cf.p * qR + tail;
-            a2 = cf.p * qF + tail;
-            a3 = cf.p * qS + tail;
-        }
-        T best = a0;
-        if (a1 > best) best = a1;
-        if (a2 > best) best = a2;
-        if (a3 > best) best = a3;
-        const uint32_t bits = q_opt_bit(a0, best, 1u) | q_opt_bit(a1, best, 2u) | q_opt_bit(a2, best, 4u) | q_opt_bit(a3, best, 0x78u);
+        T a[4];  // Q of actions 0..3 (4..6 equal action 3)
+        xyd_mix<T, SLIP>(cf, gv[(d + 3) & 3], gv[(d + 1) & 3], xyd_forward<T, ND, false>(tp, cf, d, nbv[d], (T)1), gv[d], a);
+        int arg;
+        const T best = q_argmax(a, arg);
+        const uint32_t bits = q_opt_bit(a[0], best, 1u) | q_opt_bit(a[1], best, 2u) | q_opt_bit(a[2], best, 4u) | q_opt_bit(a[3], best, 0x78u);
         opt |= (tp.valid ? bits : 0u) << (8 * d);
-        a0 = tp.valid ? a0 : (T)0;
-        a1 = tp.valid ? a1 : (T)0;
-        a2 = tp.valid ? a2 : (T)0;
-        a3 = tp.valid ? a3 : (T)0;
-        q[7 * d + 0] = a0;
-        q[7 * d + 1] = a1;
-        q[7 * d + 2] = a2;
 #pragma unroll
-        for (int a = 3; a < 7; ++a) q[7 * d + a] = a3;
+        for (int i = 0; i < 7; ++i) q[7 * d + i] = tp.valid ? a[i < 3 ? i : 3] : (T)0;
     }
     return opt;
 }
 
-// The 20 values and 4 opt bytes of direction d of a DoorKey cell (states l = d*4 + has_key*2 + door_open), in
-// dk_improve_step's operations and order.  ownD / ownL / ownR: the cell's V of direction d, d-1, d+1; nb: the
+// The 20 values and 4 opt bytes of direction d of a DoorKey cell (states l = d*4 + has_key*2 + door_open): the
+// values dk_improve_step compares.  ownD / ownL / ownR: the cell's V of direction d, d-1, d+1; nb: the
 // front cell's V of direction d; f: DkTopo::f[d].
 template <typename T>
 __device__ __forceinline__ uint32_t dk_q_step(uint32_t walk, uint32_t f, const Coef<T> &cf, const V4<T> &ownD,
@@ -100,33 +76,24 @@ __device__ __forceinline__ uint32_t dk_q_step(uint32_t walk, uint32_t f, const C
         gL[j] = cf.g * ownL.v[j];
         gR[j] = cf.g * ownR.v[j];
     }
-    const bool goal = f & 16u, lava = f & 32u, key = f & 64u, door = f & 128u;
     uint32_t opt = 0;
 #pragma unroll
     for (int hk = 0; hk < 2; ++hk) {
 #pragma unroll
         for (int dop = 0; dop < 2; ++dop) {
             const int hd = hk * 2 + dop;
-            const T qS = gD[hd], qL = gL[hd], qR = gR[hd];
-            const T qM = ((f >> hd) & 1u) ? cf.g * nb.v[hd] : qS;
-            const T qF = goal ? (T)1 : (lava ? (T)0 : qM);
-            const T qP = (!hk && key) ? gD[2 + dop] : qS;
-            const T qD = dop ? gD[hk * 2] : (hk ? gD[3] : qS);
-            const T qT = door ? qD : qS;
+            T a[5];
+            dk_q5(f, hk, dop, gL[hd], gR[hd], gD, cf.g * nb.v[hd], a);
             const bool valid = (walk >> hd) & 1u;
-            T best = qL;
-            if (qR > best) best = qR;
-            if (qF > best) best = qF;
-            if (qP > best) best = qP;
-            if (qT > best) best = qT;
-            const uint32_t bits = q_opt_bit(qL, best, 1u) | q_opt_bit(qR, best, 2u) | q_opt_bit(qF, best, 4u) |
-                                  q_opt_bit(qP, best, 8u) | q_opt_bit(qT, best, 16u);
+            int arg;
+            const T best = q_argmax(a, arg);
+            uint32_t bits = 0;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                bits |= q_opt_bit(a[i], best, 1u << i);
+                q[5 * hd + i] = valid ? a[i] : (T)0;
+            }
             opt |= (valid ? bits : 0u) << (8 * hd);
-            q[5 * hd + 0] = valid ? qL : (T)0;
-            q[5 * hd + 1] = valid ? qR : (T)0;
-            q[5 * hd + 2] = valid ? qF : (T)0;
-            q[5 * hd + 3] = valid ? qP : (T)0;
-            q[5 * hd + 4] = valid ? qT : (T)0;
         }
     }
     return opt;
