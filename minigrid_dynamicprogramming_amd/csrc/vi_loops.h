@@ -481,15 +481,7 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
         const uint32_t fl = *reinterpret_cast<const uint32_t *>(flags + (par ^ 1) * 16);
         const T fS = Vin[o1 + W], fN = Vin[o3 - W];
         const T fE = dpp_shl1_zero(in[0]), fW = dpp_shr1_zero(in[2]);
-        const T m02 = vmax(in[0], in[2]), m13 = vmax(in[1], in[3]);
-        const T m[4] = {vmax(vmax(in[0], m13), fE), vmax(vmax(in[1], m02), fS), vmax(vmax(in[2], m13), fW),
-                        vmax(vmax(in[3], m02), fN)};
-        T dm = (T)0;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            out[d] = vmax(ge * m[d], tp.tq[d]);
-            dm = vmax(dm, vabs(out[d] - in[d]));
-        }
+        const T dm = xyd_geo_sweep(ge, tp.tq, in, fE, fS, fW, fN, out);
         asm volatile("" ::"v"(dm));  // keep the arithmetic ahead of the test (no sinking past it)
         if (decltype(test)::value && fl == 0u) return false;
         diff = dm;
@@ -533,15 +525,14 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
     const T *Tp = (pos & 1) ? T0 : T1;
     const T pE = dpp_shl1_zero(vp[0]), pW = dpp_shr1_zero(vp[2]);
     if (own_cell) {
-        // forward reads the front state when the agent can enter it, else its own (xyd_step's nbv)
+        // (xyd_exit_pi_fronts<true> restated: through it vi_serve_kernel<T, XYD, serve_ew> moved)
         const T geo_f[4] = {pE, Tp[o1 + W], pW, Tp[o3 - W]};
         T nbv[4];
         V4<T> op;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             op.v[d] = vp[d];
-            const bool enter = tp.nbi[d] != d * HW + c;
-            nbv[d] = enter ? geo_f[d] : vp[d];
+            nbv[d] = xyd_enters_soa(tp, d, c, HW) ? geo_f[d] : vp[d];
         }
         V4<T> tmp;
         uint32_t pk;
@@ -561,7 +552,7 @@ __device__ __forceinline__ void fused_serve_xyd(const Geo &geo, const Coef<T> &c
 //    south fronts as fused_serve_xyd, and the values its NEIGHBOURS' sweep k+1 needs for the two
 //    planes this cell's sweep k+2 reads: plane 1 of cell c + W (planes 0, 1, 2 there and plane 1 of
 //    c + 2W) and plane 3 of cell c - W (planes 0, 2, 3 there and plane 3 of c - 2W).  So each lane
-//    computes sweep k+1 of its own cell (fused_serve_xyd's arithmetic) and those two neighbour values
+//    computes sweep k+1 of its own cell (xyd_geo_sweep, as fused_serve_xyd) and those two neighbour values
 //    (the same max of the same four V_k values, the same multiply and goal select as their owners:
 //    bit-identical), and sweep k+2 needs nothing from another lane but its east / west fronts, by
 //    DPP as in fused_serve_xyd: no cross-wave (or cross-lane LDS) exchange inside the pair.
@@ -740,19 +731,6 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
 #ifdef MGDP_SERVE_TRACE
     unsigned long long tr[6] = {0, 0, 0, 0, 0, 0};
 #endif
-    // one sweep of this lane's cell from its own values and its four geometric fronts (fused_serve_xyd's)
-    auto step = [&](const T (&in)[4], const T fE, const T fS, const T fW, const T fN, T (&out)[4]) -> T {
-        const T m02 = vmax(in[0], in[2]), m13 = vmax(in[1], in[3]);
-        const T m[4] = {vmax(vmax(in[0], m13), fE), vmax(vmax(in[1], m02), fS), vmax(vmax(in[2], m13), fW),
-                        vmax(vmax(in[3], m02), fN)};
-        T dm = (T)0;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            out[d] = vmax(ge * m[d], tq[d]);
-            dm = vmax(dm, vabs(out[d] - in[d]));
-        }
-        return dm;
-    };
     // par: this pair's flag slot (a constant at each unrolled call); test: whether a previous pair exists.
     // The sets rotate so that `mid` held V_{k-2} (dead: its planes are in Tout) and `out` holds the last
     // pair's middle set V_{k-1} until the test has passed.  half (the solve's first call): the first
@@ -781,7 +759,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
                 tr[2] = __builtin_amdgcn_s_memtime();
             }
 #endif
-            dm1 = step(in, dpp_shl1_zero(in[0]), fS, dpp_shr1_zero(in[2]), fN, mid);
+            dm1 = xyd_geo_sweep(ge, tq, in, dpp_shl1_zero(in[0]), fS, dpp_shr1_zero(in[2]), fN, mid);
             // sweep k+1 of plane 1 of c + W and plane 3 of c - W (their owners' arithmetic)
             vS = vmax(geS * vmax(vmax(s0, s2), vmax(fS, sf)), tqS);
             vN = vmax(geN * vmax(vmax(n0, n2), vmax(fN, nf)), tqN);
@@ -796,7 +774,7 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
             if ((fl & 0x01010101u) == 0u) { stop = 1; return false; }
             if ((fl & 0x02020202u) == 0u) { stop = 2; return false; }
         }
-        const T dm2 = step(mid, dpp_shl1_zero(mid[0]), vS, dpp_shr1_zero(mid[2]), vN, out);
+        const T dm2 = xyd_geo_sweep(ge, tq, mid, dpp_shl1_zero(mid[0]), vS, dpp_shr1_zero(mid[2]), vN, out);
         put(Tout, out);
         constexpr int n = HALF ? 1 : 2;  // sweeps this call computes
         // The sweep counts are made ahead of the tests, not inside their short-circuit arms: there the
@@ -871,20 +849,9 @@ __device__ __forceinline__ void fused_serve_pair(const Geo &geo, const Coef<T> &
     }
     const T pE = dpp_shl1_zero(vp[0]), pW = dpp_shr1_zero(vp[2]);
     if (own_cell) {
-        // forward reads the front state when the agent can enter it, else its own (xyd_step's nbv)
         const T geo_f[4] = {pE, pS, pW, pN};
-        const int HWs = geo.HWs;
-        T nbv[4];
-        V4<T> op;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            op.v[d] = vp[d];
-            const bool enter = tp.nbi[d] != d * HWs + c;
-            nbv[d] = enter ? geo_f[d] : vp[d];
-        }
         V4<T> tmp;
-        uint32_t pk;
-        xyd_step<T, false, true>(tp, cf, op, nbv, tmp, pk);
+        const uint32_t pk = xyd_exit_pi_fronts<true>(tp, cf, vp, geo_f, c, geo.HWs, tmp);
         *reinterpret_cast<uint32_t *>(pig + c * 4) = pk;
         *reinterpret_cast<V4<T> *>(Vg_out + c * 4) = V4<T>{{vk[0], vk[1], vk[2], vk[3]}};
     }
@@ -1053,13 +1020,7 @@ __device__ __forceinline__ void fused_pair_xyd(const Geo &geo, const Coef<T> &cf
         T d = (T)0;
         T o[2][4];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const T m02 = vmax(in[j][0], in[j][2]), m13 = vmax(in[j][1], in[j][3]);
-            const T m[4] = {vmax(vmax(in[j][0], m13), F[j][0]), vmax(vmax(in[j][1], m02), F[j][1]),
-                            vmax(vmax(in[j][2], m13), F[j][2]), vmax(vmax(in[j][3], m02), F[j][3])};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[j][q] = ge[j] * m[q];
-        }
+        for (int j = 0; j < 2; ++j) xyd_geo_scaled(ge[j], in[j], F[j][0], F[j][1], F[j][2], F[j][3], o[j]);
         // the goal's reward max(fl(g * m), 1) is exactly 1 (values are <= 1): a select (uniform
         // branch: few waves have one)
         if (goal_wave) {
@@ -1334,11 +1295,7 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
         for (int j = 0; j < P; ++j) {
             const T FE = (j + 1 < P && lane == 63) ? R[j + 1] : R[j];
             const T FW = (j > 0 && lane == 0) ? L[j - 1] : L[j];
-            const T m02 = vmax(in[j][0], in[j][2]), m13 = vmax(in[j][1], in[j][3]);
-            const T m[4] = {vmax(vmax(in[j][0], m13), FE), vmax(vmax(in[j][1], m02), FS[j]),
-                            vmax(vmax(in[j][2], m13), FW), vmax(vmax(in[j][3], m02), FN[j])};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[j][q] = ge[j] * m[q];
+            xyd_geo_scaled(ge[j], in[j], FE, FS[j], FW, FN[j], o[j]);
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -1394,15 +1351,8 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
                                 (j > 0 && lane == 0) ? L[j - 1] : L[j], N3[c - W]};
             if (c < geo.HW) {
                 const XydTopo<T> tp = xyd_topo<T>(cl, geo, c);
-                V4<T> op, tmp;
-                T nbv[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    op.v[d] = prv[j][d];
-                    nbv[d] = (tp.nbi[d] >> 2) != c ? front[d] : prv[j][d];  // blocked / terminal: own state
-                }
-                uint32_t pk;
-                xyd_step<T, false, true>(tp, cf, op, nbv, tmp, pk);
+                V4<T> tmp;
+                const uint32_t pk = xyd_exit_pi_fronts<false>(tp, cf, prv[j], front, c, 0, tmp);
                 store_pi_exit(pig + c * 4, pk, WT);
                 store_v4_exit(Vg_out + c * 4, V4<T>{{cur[j][0], cur[j][1], cur[j][2], cur[j][3]}}, WT);
             }
@@ -1431,8 +1381,8 @@ __device__ __forceinline__ void fused_wave2_xyd(const Geo &geo, const Coef<T> &c
 // values between lanes (ds_bpermute: the band-edge fronts) and touches no LDS tile at all --
 // fused_wave2_xyd's row-major blocks read 2P and write 2P LDS words per sweep, a round trip on
 // every sweep's critical path that left FourRooms x 4096 (4 waves per SIMD) stalled half the time.
-// Same one-multiply backup, geometric fronts (invalid states hold +0), goal reward, ballot stop
-// rule, uncommitted last sweep and per-action pi pass as fused_wave2_xyd: bit-identical V, pi and
+// Same one-multiply backup (xyd_geo_scaled), geometric fronts (invalid states hold +0), goal reward, ballot
+// stop rule, uncommitted last sweep and per-action pi pass (xyd_exit_pi_fronts) as fused_wave2_xyd: bit-identical V, pi and
 // sweep counts.  Grids with W <= 64 and ceil(H / (64 / W)) <= 8.
 template <typename T>
 __device__ __forceinline__ T lane_shfl(T v, int src) {  // lane src's v (ds_bpermute, no LDS memory)
@@ -1505,13 +1455,7 @@ __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf
         fronts(in, FE, FS, FW, FN);
         T o[HB][4];
 #pragma unroll
-        for (int j = 0; j < HB; ++j) {
-            const T m02 = vmax(in[j][0], in[j][2]), m13 = vmax(in[j][1], in[j][3]);
-            const T m[4] = {vmax(vmax(in[j][0], m13), FE[j]), vmax(vmax(in[j][1], m02), FS[j]),
-                            vmax(vmax(in[j][2], m13), FW[j]), vmax(vmax(in[j][3], m02), FN[j])};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[j][q] = ge[j] * m[q];
-        }
+        for (int j = 0; j < HB; ++j) xyd_geo_scaled(ge[j], in[j], FE[j], FS[j], FW[j], FN[j], o[j]);
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
             if ((goal_slots >> j) & 1u) {  // the goal's reward max(fl(g * m), 1) is exactly 1 (values are <= 1): a select
@@ -1567,12 +1511,13 @@ __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf
         if (c >= 0) {
             const XydTopo<T> tp = xyd_topo<T>(cl, geo, c);
             const T front[4] = {FE[j], FS[j], FW[j], FN[j]};
+            // (xyd_exit_pi_fronts<false> restated: through it vi_serve_kernel / vi_fused_kernel<T, XYD, band, N> moved)
             V4<T> op, tmp;
             T nbv[4];
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 op.v[d] = prev[j][d];
-                nbv[d] = (tp.nbi[d] >> 2) != c ? front[d] : prev[j][d];  // blocked / terminal: own state
+                nbv[d] = xyd_enters(tp, d, c) ? front[d] : prev[j][d];
             }
             uint32_t pk;
             xyd_step<T, false, true>(tp, cf, op, nbv, tmp, pk);
@@ -1590,7 +1535,7 @@ __device__ __forceinline__ void fused_band_xyd(const Geo &geo, const Coef<T> &cf
 // other), the two east / west values that cross the wave boundary (plane 0 of wave 1's first
 // cell, plane 2 of wave 0's last cell) go through two LDS words per tile, and each wave's stop
 // ballot through a flag word per tile, read with the next sweep's fronts -- so both waves take
-// the same stop decision.  Arithmetic, rule and pi pass as fused_wave2_xyd: bit-identical results.
+// the same stop decision.  Arithmetic, rule and pi pass (xyd_exit_pi_fronts) as fused_wave2_xyd: bit-identical results.
 // LDS: [slots 256 B][cells HWp][tile 0][tile 1][edges 4 T | dV 2 T | flags 4 u32] (wave2n_*).
 
 template <typename T, bool LOCAL, int PW, typename Done>
@@ -1670,6 +1615,7 @@ __device__ __forceinline__ void fused_wave2n_xyd(const Geo &geo, const Coef<T> &
             // across the wave boundary: wave 0's last cell and wave 1's first cell through LDS
             const T FE = lane == 63 ? (j + 1 < PW ? R[j + 1] : (w == 0 ? eE : R[j])) : R[j];
             const T FW = lane == 0 ? (j > 0 ? L[j - 1] : (w == 1 ? eW : L[j])) : L[j];
+            // (xyd_geo_scaled restated: through it vi_fused_kernel<float, XYD, mix, 2> moved)
             const T m02 = vmax(in[j][0], in[j][2]), m13 = vmax(in[j][1], in[j][3]);
             const T m[4] = {vmax(vmax(in[j][0], m13), FE), vmax(vmax(in[j][1], m02), FS[j]),
                             vmax(vmax(in[j][2], m13), FW), vmax(vmax(in[j][3], m02), FN[j])};
@@ -1746,15 +1692,8 @@ __device__ __forceinline__ void fused_wave2n_xyd(const Geo &geo, const Coef<T> &
                                 lane == 0 ? (j > 0 ? L[j - 1] : (w == 1 ? eW : L[j])) : L[j], N3[c - W]};
             if (c < geo.HW) {
                 const XydTopo<T> tp = xyd_topo<T>(cl, geo, c);
-                V4<T> op, tmp;
-                T nbv[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    op.v[d] = prv[j][d];
-                    nbv[d] = (tp.nbi[d] >> 2) != c ? front[d] : prv[j][d];  // blocked / terminal: own state
-                }
-                uint32_t pk;
-                xyd_step<T, false, true>(tp, cf, op, nbv, tmp, pk);
+                V4<T> tmp;
+                const uint32_t pk = xyd_exit_pi_fronts<false>(tp, cf, prv[j], front, c, 0, tmp);
                 *reinterpret_cast<uint32_t *>(pig + c * 4) = pk;
                 *reinterpret_cast<V4<T> *>(Vg_out + c * 4) = V4<T>{{cur[j][0], cur[j][1], cur[j][2], cur[j][3]}};
             }
@@ -2079,6 +2018,7 @@ __device__ __forceinline__ T dk_rows_step(uint32_t walk, const uint32_t (&f)[4],
     T df[16];
 #pragma unroll
     for (int hd = 0; hd < 4; ++hd) {
+        // (xyd_geo_max's sharing in DoorKey's indexing: the key / door selects sit between the pair and the front)
         const T m02 = vmax(in[hd], in[8 + hd]), m13 = vmax(in[4 + hd], in[12 + hd]);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {

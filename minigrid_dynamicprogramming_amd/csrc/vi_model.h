@@ -252,6 +252,38 @@ __device__ __forceinline__ T q_argmax(const T (&q)[N], I &arg) {
     return best;
 }
 
+// The deterministic sweep on geometric fronts, stated once: m[d] = max(V[d-1], V[d],
+// V[d+1], F[d]), what left, right, self and forward read from direction d, the turns' pair shared between
+// opposite directions.  in = V_{k-1} of the cell's four states; fE, fS, fW, fN = what forward reads from
+// direction 0..3 (a front the agent cannot enter holds +0 or is the state's own value: the same maximum).
+template <typename T>
+__device__ __forceinline__ void xyd_geo_max(const T (&in)[4], T fE, T fS, T fW, T fN, T (&m)[4]) {
+    const T m02 = vmax(in[0], in[2]), m13 = vmax(in[1], in[3]);
+    m[0] = vmax(vmax(in[0], m13), fE), m[1] = vmax(vmax(in[1], m02), fS);
+    m[2] = vmax(vmax(in[2], m13), fW), m[3] = vmax(vmax(in[3], m02), fN);
+}
+// The batched loops' backup without the goal: o[d] = fl(ge * m[d]), ge = g or 0 (absorbing cell).
+template <typename T>
+__device__ __forceinline__ void xyd_geo_scaled(T ge, const T (&in)[4], T fE, T fS, T fW, T fN, T (&o)[4]) {
+    T m[4];
+    xyd_geo_max(in, fE, fS, fW, fN, m);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = ge * m[d];
+}
+// The served loops' whole sweep of one cell: out[d] = max(fl(ge * m[d]), tq[d]); returns max |dV|.
+template <typename T>
+__device__ __forceinline__ T xyd_geo_sweep(T ge, const T (&tq)[4], const T (&in)[4], T fE, T fS, T fW, T fN, T (&out)[4]) {
+    T m[4];
+    xyd_geo_max(in, fE, fS, fW, fN, m);
+    T dm = (T)0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        out[d] = vmax(ge * m[d], tq[d]);
+        dm = vmax(dm, vabs(out[d] - in[d]));
+    }
+    return dm;
+}
+
 template <typename T, bool SLIP, bool WRITE_PI, bool ND = false, bool FH = false>
 __device__ __forceinline__ T xyd_step(const XydTopo<T> &tp, const Coef<T> &cf, const V4<T> &own,
                                       const T (&nbv)[4], V4<T> &out, uint32_t &pk, T rg = (T)1) {
@@ -268,9 +300,8 @@ __device__ __forceinline__ T xyd_step(const XydTopo<T> &tp, const Coef<T> &cf, c
         T f[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d) f[d] = (ND && ((tp.lavaF >> d) & 1u)) ? own.v[d] : nbv[d];
-        const T m02 = vmax(own.v[0], own.v[2]), m13 = vmax(own.v[1], own.v[3]);
-        const T m[4] = {vmax(vmax(own.v[0], m13), f[0]), vmax(vmax(own.v[1], m02), f[1]),
-                        vmax(vmax(own.v[2], m13), f[2]), vmax(vmax(own.v[3], m02), f[3])};
+        T m[4];
+        xyd_geo_max(own.v, f[0], f[1], f[2], f[3], m);
         T dv = (T)0;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
@@ -307,6 +338,30 @@ __device__ __forceinline__ T xyd_step(const XydTopo<T> &tp, const Coef<T> &cf, c
         dv = vmax(dv, vabs(best - own.v[d]));
     }
     return dv;
+}
+
+// May the agent enter the cell ahead of cell c in direction d (else forward reads the state's own value)?
+// xyd_enters: on the cell-major topology (xyd_topo); xyd_enters_soa: on xyd_topo_soa's, plane stride HWs.
+template <typename T>
+__device__ __forceinline__ bool xyd_enters(const XydTopo<T> &tp, int d, int c) { return (tp.nbi[d] >> 2) != c; }
+template <typename T>
+__device__ __forceinline__ bool xyd_enters_soa(const XydTopo<T> &tp, int d, int c, int HWs) { return tp.nbi[d] != d * HWs + c; }
+// The policy pass that ends a solve, from geometric fronts: pk = the per-action argmax (xyd_step) on vprev =
+// V_{k-1} of cell c with front[d] where the agent enters and its own value elsewhere.  vk: the step's V_k
+// (what a caller without V_k of its own, as the depth form, stores).  The caller stores pk and V_k.
+template <bool SOA, typename T>
+__device__ __forceinline__ uint32_t xyd_exit_pi_fronts(const XydTopo<T> &tp, const Coef<T> &cf, const T *vprev,
+                                                       const T (&front)[4], int c, int HWs, V4<T> &vk) {
+    V4<T> op;
+    T nbv[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        op.v[d] = vprev[d];
+        nbv[d] = (SOA ? xyd_enters_soa(tp, d, c, HWs) : xyd_enters(tp, d, c)) ? front[d] : vprev[d];
+    }
+    uint32_t pk;
+    xyd_step<T, false, true>(tp, cf, op, nbv, vk, pk);
+    return pk;
 }
 
 // DoorKey cell topology: own walkability per (has_key, door_open) and, per direction, the front

@@ -250,6 +250,7 @@ __device__ __forceinline__ int fused_serve_depth(const Geo &geo, const Coef<T> &
     // the last sweep, for real: fused_serve_pair's policy pass on V_{K-1}; its output is V_K
     const T pE = dpp_shl1_zero(v[0]), pW = dpp_shr1_zero(v[2]);
     if (own_cell) {
+        // (xyd_exit_pi_fronts<true> restated: through it vi_serve_kernel<T, XYD, serve_pair + depth> moved)
         const T geo_f[4] = {pE, v[4], pW, v[5]};
         const int HWs = geo.HWs;
         T nbv[4];
@@ -257,8 +258,7 @@ __device__ __forceinline__ int fused_serve_depth(const Geo &geo, const Coef<T> &
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             op.v[d] = v[d];
-            const bool enter = tp.nbi[d] != d * HWs + c;
-            nbv[d] = enter ? geo_f[d] : v[d];
+            nbv[d] = xyd_enters_soa(tp, d, c, HWs) ? geo_f[d] : v[d];
         }
         V4<T> vk;
         uint32_t pk;
