@@ -9,17 +9,10 @@
 #include <string>
 
 #include "../../include/mgdp.h"
+#include "constants.h"
 #include "vi_layout.h"
 
 namespace mgdp {
-
-// OBJECT_TO_IDX, minigrid/core/constants.py:25-37
-enum : int {
-    T_UNSEEN = 0, T_EMPTY = 1, T_WALL = 2, T_FLOOR = 3, T_DOOR = 4, T_KEY = 5, T_BALL = 6,
-    T_BOX = 7, T_GOAL = 8, T_LAVA = 9, T_AGENT = 10
-};
-enum : int { C_GREY = 5 };                               // COLOR_TO_IDX, constants.py:20
-enum : int { D_OPEN = 0, D_CLOSED = 1, D_LOCKED = 2 };   // STATE_TO_IDX, constants.py:42-46
 
 void set_error(const char *fmt, ...);
 

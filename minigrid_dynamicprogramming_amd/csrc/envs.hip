@@ -19,6 +19,14 @@
 // never materialised: view cell (i, j) maps to world top_left - f*j + r*i (f = DIR_TO_VEC[dir],
 // r = right_vec, minigrid_env.py:421-446), which equals the reference's slice + (dir+1) x
 // rotate_left; process_vis runs on a 64-bit visibility mask.
+//
+// Device code: the step kernel and the masked load's kernel here, envs_rollout.h (policy lookup, the
+// fused rollout, the slip streams) and envs_qlearn.h (tabular Q-learning).  envs_codec.h (host-plain)
+// is the cell code, the conversions between Grid.encode() layout and the planes, and the masked
+// load's staging layout; timed.h the pooled event pairs of timed launches.  The host side: envs_host.h
+// (the handle, launch_timed, the step launch, the grow-on-demand scratch), envs_host_state.h (load,
+// get / set state, Box contents) and envs_host_episode.h (rollout, slip, explore, Q-learning: checks,
+// kernel selection, host staging); this file holds the C ABI.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -26,7 +34,9 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "envs_codec.h"
 #include "pcg64.h"
+#include "timed.h"
 
 namespace mgdp {
 
@@ -38,22 +48,6 @@ struct EnvGeo {
     uint32_t nd_mask;   // NoDeath (wrappers.py:799-872): bit t = OBJECT_TO_IDX type t is a no-death type
     double death_cost;
 };
-
-// One-byte cell code.  Grid.encode() (grid.py:244-268) gives every cell (type, colour, state) with
-// type <= 10, colour <= 5 and state != 0 only for doors (WorldObj.encode returns state 0,
-// Door.encode :197-213 open 0 / closed 1 / locked 2), so a cell fits a byte: type*8 + colour, or
-// 0x80 | state*8 + colour for a door.  One plane instead of three cuts the bytes the view windows
-// pull from HBM by 3x (the window rows are read at cache-line granularity, i.e. most of each grid).
-__host__ __device__ inline uint32_t cell_code(int t, int c, int s) {
-    return t == T_DOOR ? 0x80u | ((uint32_t)s << 3) | (uint32_t)c : ((uint32_t)t << 3) | (uint32_t)c;
-}
-__host__ __device__ inline void cell_decode(uint32_t code, int &t, int &c, int &s) {
-    const bool door = (code & 0x80u) != 0;
-    t = door ? (int)T_DOOR : (int)(code >> 3);
-    c = (int)(code & 7u);
-    s = door ? (int)((code >> 3) & 3u) : 0;
-}
-constexpr uint32_t kCodeWall = (uint32_t)T_WALL * 8u + (uint32_t)C_GREY;  // padding / out-of-grid filler
 
 // MGDP_STEP_NT: bit 0 = the obs tile leaves with nontemporal stores, bit 1 = the window rows are
 // read with nontemporal loads (both streams are touched once per step; past the MALL at 2^20 envs)
@@ -403,320 +397,43 @@ envs_step_kernel(EnvGeo g, uint8_t *__restrict__ CELL, int32_t *__restrict__ age
 #include "envs_rollout.h"  // tabular policies on resident envs: policy lookup and the fused rollout
 #include "envs_qlearn.h"   // tabular Q-learning on resident envs, episode restarts inside the launch
 
+// A masked reset (state_load, envs_host_state.h): one block per env writes a masked env's cells, agent,
+// carry, max_steps and see_through from the staging buffer st (StageLayout, envs_codec.h) and clears its
+// Box contents.
+extern "C" __global__ void __launch_bounds__(64)
+envs_masked_load_kernel(int B, int HWp, const uint8_t *__restrict__ st, uint8_t *__restrict__ cell, int32_t *__restrict__ agent,
+                        int32_t *__restrict__ carry, int32_t *__restrict__ maxs, uint8_t *__restrict__ see,
+                        uint8_t *__restrict__ cont, uint8_t *__restrict__ ccont) {
+    const int b = blockIdx.x;
+    const StageLayout L{B, HWp};
+    if (!st[L.mask(b)]) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(L.cells(st) + (size_t)b * HWp);
+    uint4 *dst = reinterpret_cast<uint4 *>(cell + (size_t)b * HWp);
+    for (int i = threadIdx.x; i < HWp / 16; i += blockDim.x) {
+        dst[i] = src[i];
+        if (cont) reinterpret_cast<uint4 *>(cont + (size_t)b * HWp)[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (threadIdx.x == 0) {
+        const int32_t *ag = L.agent(st), *cr = L.carry(st), *ms = L.max(st);
+        for (int j = 0; j < 4; ++j) agent[4 * b + j] = ag[4 * b + j];
+        carry[2 * b] = cr[2 * b];
+        carry[2 * b + 1] = cr[2 * b + 1];
+        maxs[b] = ms[b];
+        see[b] = st[L.see(b)];
+        if (ccont) ccont[b] = 0;
+    }
+}
+
 }  // namespace mgdp
 
+// ================================================================================================
+// Host side
+// ================================================================================================
 using namespace mgdp;
 
-// One set of per-env PCG64 records, allocated by its first seeding.
-struct StreamTable {
-    uint64_t *state = nullptr;  // [B][4] state hi, lo, inc hi, lo
-    uint32_t *half = nullptr;   // [B][2] has_uint32, uinteger
-    bool on = false;            // seeded: until then a seeding takes no mask
-};
-
-struct mgdp_envs {
-    int device = 0, B = 0, W = 0, H = 0, HW = 0, HWp = 0, vs = 7;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint8_t *d_cell = nullptr, *d_see = nullptr;  // d_cell: one-byte cell codes [B][HWp]
-    uint8_t *d_cont = nullptr, *d_ccont = nullptr;  // Box contents planes (mgdp_envs_set_contents), else null
-    int32_t *d_agent = nullptr, *d_carry = nullptr, *d_max = nullptr, *d_act = nullptr, *d_dir = nullptr,
-            *d_status = nullptr;
-    uint8_t *d_obs = nullptr, *d_term = nullptr, *d_trunc = nullptr;
-    double *d_rew = nullptr;
-    uint32_t nd_mask = 0;
-    // masked loads (auto-reset of some envs): one staging copy + envs_masked_load_kernel
-    uint8_t *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    double death_cost = -1.0;
-    int group = 2;  // lanes per env in envs_step_kernel (MGDP_STEP_GROUP = 1, 2, 4 or 8; 2 measured fastest)
-    // rollouts (envs_rollout.h): host-call scratch (the policy and the trace), grown on demand;
-    // roll_reader: -1 = LDS planes whenever 64 of them fit, 0 / 1 = MGDP_ROLLOUT_READER=hbm / lds
-    uint8_t *d_roll = nullptr;
-    size_t roll_bytes = 0;
-    int roll_reader = -1;
-    // the slip streams and Q-learning's explore streams (section 18)
-    StreamTable slip, explore;
-    double slip_p = 1.0;
-    int slip_ra = -1;
-    uint8_t *d_stream_mask = nullptr;  // [B] a masked reseed's mask (either table)
-    // step-kernel timing (mgdp_envs_enable_timing): pooled event pairs handed to hipExtLaunchKernelGGL
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
-    double total_ms = 0.0;
-    long long launches = 0;
-};
-
-namespace {
-
-int timed_collect(mgdp_envs *E) {  // after a stream sync
-    for (auto &p : E->ev) {
-        float ms = 0.f;
-        MGDP_HIP(hipEventElapsedTime(&ms, p.first, p.second));
-        E->total_ms += ms;
-        E->launches += 1;
-        E->ev_pool.push_back(p);
-    }
-    E->ev.clear();
-    return 0;
-}
-
-EnvGeo env_geo(const mgdp_envs *E) { return EnvGeo{E->B, E->W, E->H, E->HWp, E->vs, E->nd_mask, E->death_cost}; }
-
-// The event pair of the next timed launch (null, null with timing off).
-int timing_pair(mgdp_envs *E, hipEvent_t &ta, hipEvent_t &tb) {
-    ta = tb = nullptr;
-    if (E->timing) {
-        if (E->ev.size() >= 4096) {  // bound the pending pairs
-            MGDP_HIP(hipStreamSynchronize(E->stream));
-            if (int rc = timed_collect(E)) return rc;
-        }
-        std::pair<hipEvent_t, hipEvent_t> p;
-        if (!E->ev_pool.empty()) {
-            p = E->ev_pool.back();
-            E->ev_pool.pop_back();
-        } else {
-            MGDP_HIP(hipEventCreate(&p.first));
-            MGDP_HIP(hipEventCreate(&p.second));
-        }
-        E->ev.push_back(p);
-        ta = p.first;
-        tb = p.second;
-    }
-    return 0;
-}
-
-int launch_step(mgdp_envs *E, const int32_t *d_act, uint8_t *d_obs, int32_t *d_dir, double *d_rew,
-                uint8_t *d_term, uint8_t *d_trunc, int32_t *d_status, int observe_only) {
-    const int ne = kGroupBlock / E->group;
-    const int grid = (E->B + ne - 1) / ne;
-    const int smem = (int)round_up(ne * E->vs * E->vs * 3, 16) + ne * ((E->vs + 1) * kWinRow + 4);
-    auto pick = [&](auto k7, auto k5, auto k3) { return E->vs == 7 ? k7 : E->vs == 5 ? k5 : k3; };
-    auto k = E->group == 8   ? pick(envs_step_kernel<7, 8>, envs_step_kernel<5, 8>, envs_step_kernel<3, 8>)
-             : E->group == 4 ? pick(envs_step_kernel<7, 4>, envs_step_kernel<5, 4>, envs_step_kernel<3, 4>)
-             : E->group == 1 ? pick(envs_step_kernel<7, 1>, envs_step_kernel<5, 1>, envs_step_kernel<3, 1>)
-                             : pick(envs_step_kernel<7, 2>, envs_step_kernel<5, 2>, envs_step_kernel<3, 2>);
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3(grid), dim3(kGroupBlock), smem, E->stream, ta, tb, 0, env_geo(E), E->d_cell, E->d_agent,
-                       E->d_carry, E->d_cont, E->d_ccont, E->d_max, E->d_see, d_act, d_obs, d_dir, d_rew, d_term, d_trunc, d_status,
-                       observe_only);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- tabular policies on resident envs (envs_rollout.h) --------------------
-constexpr int kRollLdsMax = 160 * 1024 - 2048;  // the 64 padded planes; the rest is the staging pass's words
-
-int model_states(const mgdp_envs *E, int32_t model) { return E->W * E->H * (model == MGDP_MODEL_XYD ? 4 : 16); }
-
-int roll_check(const mgdp_envs *E, int32_t model, const void *pi, int32_t T, int *S) {
-    MGDP_CHECK(E && pi, MGDP_E_INVALID, "null argument");
-    MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
-    MGDP_CHECK(T >= 1, MGDP_E_INVALID, "T must be >= 1 (1 = a stationary policy), got %d", T);
-    MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
-    *S = model_states(E, model);
-    return 0;
-}
-
-// The episode kernels' cell reader: LDS planes wherever a wave's 64 fit, unless MGDP_ROLLOUT_READER says hbm.
-bool roll_on_lds(const mgdp_envs *E) {
-    const bool fits = kRollWave * roll_stride(E->HWp) <= kRollLdsMax;
-    return E->roll_reader < 0 ? fits : (E->roll_reader == 1 && fits);
-}
-
-// A trace: states [len][B] and actions [len][B], or none (null, null, 0).
-struct TraceBufs {
-    int32_t *state;
-    int8_t *act;
-    int len;
-};
-
-// Device buffers: both or neither.
-int trace_device(int32_t *state, int8_t *act, int32_t len, TraceBufs *t) {
-    const bool trace = state && act;
-    MGDP_CHECK(trace || (!state && !act), MGDP_E_INVALID, "a trace needs both of its buffers");
-    *t = trace ? TraceBufs{state, act, len} : TraceBufs{nullptr, nullptr, 0};
-    return 0;
-}
-
-// Host buffers: both and len > 0, or else none is used.
-int trace_host(int32_t *state, int8_t *act, int32_t len, TraceBufs *t) {
-    const bool trace = state && act && len > 0;
-    MGDP_CHECK(trace || (!state && !act) || len == 0, MGDP_E_INVALID, "a trace needs both of its buffers");
-    *t = trace ? TraceBufs{state, act, len} : TraceBufs{nullptr, nullptr, 0};
-    return 0;
-}
-
-// One wave per 64 envs (envs_rollout_kernel, envs_qlearn_kernel): smem bytes of dynamic LDS, the trace
-// cleared to -1 (entries no step fills stay so), the launch timed like every other.  args follow the
-// env's own buffers in the kernel's signature.
-template <typename K, typename... Args>
-int launch_episode(mgdp_envs *E, K k, int smem, const TraceBufs &t, const Args &...args) {
-    if (smem > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    if (t.len > 0) {
-        MGDP_HIP(hipMemsetAsync(t.state, 0xff, sizeof(int32_t) * (size_t)t.len * E->B, E->stream));
-        MGDP_HIP(hipMemsetAsync(t.act, 0xff, (size_t)t.len * E->B, E->stream));
-    }
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3((E->B + kRollWave - 1) / kRollWave), dim3(kRollWave), smem, E->stream, ta, tb, 0, env_geo(E),
-                          E->d_cell, E->d_agent, E->d_carry, E->d_max, args...);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-// One device-to-host copy on the handle's stream; a null dst is an output the caller did not ask for.
-int download(mgdp_envs *E, void *dst, const void *src, size_t bytes) {
-    if (dst) MGDP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, E->stream));
-    return 0;
-}
-
-int launch_policy_actions(mgdp_envs *E, int32_t model, const int8_t *d_pi, int32_t T, int S, int32_t *d_actions,
-                          int32_t *d_status) {
-    auto k = model == MGDP_MODEL_XYD ? envs_policy_actions_kernel<kRollXYD> : envs_policy_actions_kernel<kRollDoorKey>;
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, ta, tb, 0, env_geo(E), E->d_cell, E->d_agent,
-                          E->d_carry, d_pi, T, S, d_actions, d_status);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-SlipArgs slip_args(const mgdp_envs *E) { return SlipArgs{E->slip_p, E->slip_ra, E->slip.state, E->slip.half}; }
-SlipArgs explore_args(const mgdp_envs *E) { return SlipArgs{1.0, -1, E->explore.state, E->explore.half}; }
-
-using RolloutKernel = void (*)(EnvGeo, uint8_t *, int32_t *, int32_t *, const int32_t *, RolloutArgs, SlipArgs);
-template <bool SLIP>
-RolloutKernel rollout_kernel(int32_t model, bool lds) {
-    return model == MGDP_MODEL_XYD ? (lds ? envs_rollout_kernel<kRollXYD, true, SLIP> : envs_rollout_kernel<kRollXYD, false, SLIP>)
-                                   : (lds ? envs_rollout_kernel<kRollDoorKey, true, SLIP>
-                                          : envs_rollout_kernel<kRollDoorKey, false, SLIP>);
-}
-
-int launch_rollout(mgdp_envs *E, int32_t model, const RolloutArgs &r) {
-    const bool lds = roll_on_lds(E);
-    const RolloutKernel k = E->slip.on ? rollout_kernel<true>(model, lds) : rollout_kernel<false>(model, lds);
-    return launch_episode(E, k, lds ? kRollWave * roll_stride(E->HWp) : 0, TraceBufs{r.tr_state, r.tr_act, r.trace_len}, r,
-                          slip_args(E));
-}
-
-int launch_slip_actions(mgdp_envs *E, const int32_t *d_in, int32_t *d_out) {
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(envs_slip_actions_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, ta, tb, 0, E->B,
-                          slip_args(E), d_in, d_out);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-int roll_scratch(mgdp_envs *E, size_t need) {
-    if (E->roll_bytes >= need) return 0;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    if (E->d_roll) MGDP_HIP(hipFree(E->d_roll));
-    E->d_roll = nullptr;
-    E->roll_bytes = 0;
-    MGDP_HIP(hipMalloc((void **)&E->d_roll, need));
-    E->roll_bytes = need;
-    return 0;
-}
-
-// A bump allocator over d_roll: take() lays the pieces of a host call out, each from a 16-byte boundary;
-// roll_scratch(E, end) then makes d_roll hold them all, and roll_at<T>() is a piece's address.
-struct RollCursor {
-    size_t end = 0;
-    size_t take(size_t bytes) {
-        const size_t off = end;
-        end += round_up(bytes, 16);
-        return off;
-    }
-};
-template <typename T>
-T *roll_at(const mgdp_envs *E, size_t off) { return reinterpret_cast<T *>(E->d_roll + off); }
-
-// ---- stream tables: slip and explore (DESIGN.md sections 17 and 18) -------------------------------
-// Stream b of the table becomes default_rng(seed0 + b); mask [B] (host) keeps the streams of its zero
-// entries.  entry names the caller in the refusal of a masked first seeding.
-int seed_streams(mgdp_envs *E, StreamTable &t, uint64_t seed0, const uint8_t *mask, const char *entry) {
-    MGDP_CHECK(t.on || !mask, MGDP_E_INVALID, "the first %s seeds every stream: no mask", entry);
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (!t.state) MGDP_HIP(hipMalloc((void **)&t.state, sizeof(uint64_t) * 4 * B));
-    if (!t.half) MGDP_HIP(hipMalloc((void **)&t.half, sizeof(uint32_t) * 2 * B));
-    if (mask) {
-        if (!E->d_stream_mask) MGDP_HIP(hipMalloc((void **)&E->d_stream_mask, B));
-        MGDP_HIP(hipMemcpyAsync(E->d_stream_mask, mask, B, hipMemcpyHostToDevice, E->stream));
-    }
-    hipLaunchKernelGGL(envs_slip_seed_kernel, dim3((E->B + 255) / 256), dim3(256), 0, E->stream, E->B, seed0,
-                       mask ? E->d_stream_mask : nullptr, SlipArgs{1.0, -1, t.state, t.half});
-    MGDP_HIP(hipGetLastError());
-    if (mask) MGDP_HIP(hipStreamSynchronize(E->stream));  // the caller's mask may go once this returns
-    t.on = true;
-    return 0;
-}
-
-int read_streams(mgdp_envs *E, const StreamTable &t, uint64_t *state, uint32_t *half) {
-    DeviceGuard guard(E->device);
-    const size_t B = E->B;
-    if (download(E, state, t.state, sizeof(uint64_t) * 4 * B) || download(E, half, t.half, sizeof(uint32_t) * 2 * B))
-        return MGDP_E_HIP;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
-}
-
-// ---- tabular Q-learning on resident envs (envs_qlearn.h) --------------------
-int q_model_check(const mgdp_envs *E, int32_t model, int32_t n_act, int *S, int *A) {
-    MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
-    MGDP_CHECK(model == MGDP_MODEL_XYD || model == MGDP_MODEL_DOORKEY, MGDP_E_INVALID, "unknown model %d", model);
-    *A = model == MGDP_MODEL_XYD ? 7 : 5;
-    *S = model_states(E, model);
-    MGDP_CHECK(n_act >= 1 && n_act <= *A, MGDP_E_INVALID, "n_act must be in 1..%d, got %d", *A, n_act);
-    return 0;
-}
-
-int q_learn_check(const mgdp_envs *E, int32_t model, int32_t n_steps, double alpha, double gamma, double eps, int32_t n_act,
-                  int32_t unit_goal, int32_t trace_len, int *S, int *A) {
-    if (int rc = q_model_check(E, model, n_act, S, A)) return rc;
-    MGDP_CHECK(n_steps > 0, MGDP_E_INVALID, "n_steps must be > 0, got %d", n_steps);
-    MGDP_CHECK(eps >= 0.0 && eps <= 1.0, MGDP_E_INVALID, "eps must be in [0, 1], got %g", eps);  // NaN fails both
-    MGDP_CHECK(alpha == alpha && gamma == gamma, MGDP_E_INVALID, "alpha and gamma must not be NaN");
-    MGDP_CHECK(unit_goal == 0 || unit_goal == 1, MGDP_E_INVALID, "unit_goal must be 0 or 1, got %d", unit_goal);
-    MGDP_CHECK(trace_len >= 0, MGDP_E_INVALID, "trace_len must be >= 0, got %d", trace_len);
-    MGDP_CHECK(E->explore.on, MGDP_E_INVALID, "no explore streams on this handle (mgdp_envs_set_explore)");
-    MGDP_CHECK(!E->d_cont, MGDP_E_UNSUPPORTED, "Box contents planes are in use on this handle: outside both models");
-    MGDP_CHECK(model == MGDP_MODEL_XYD || kRollWave * roll_stride(E->HWp) <= kRollLdsMax, MGDP_E_UNSUPPORTED,
-               "DoorKey Q-learning restores mutated planes from HBM into LDS: 64 planes of %d x %d do not fit", E->W, E->H);
-    return 0;
-}
-
-using QLearnKernel = void (*)(EnvGeo, const uint8_t *, const int32_t *, const int32_t *, const int32_t *, QLearnArgs, SlipArgs,
-                              SlipArgs);
-template <bool SLIP>
-QLearnKernel qlearn_kernel(int32_t model, bool lds) {
-    return model == MGDP_MODEL_DOORKEY ? envs_qlearn_kernel<kRollDoorKey, true, SLIP>
-           : lds                       ? envs_qlearn_kernel<kRollXYD, true, SLIP>
-                                       : envs_qlearn_kernel<kRollXYD, false, SLIP>;
-}
-
-int launch_qlearn(mgdp_envs *E, int32_t model, const QLearnArgs &q) {
-    // MGDP_ROLLOUT_READER chooses the XYD reader as for the rollout; DoorKey always steps on LDS (q_learn_check)
-    const bool lds = model == MGDP_MODEL_DOORKEY || roll_on_lds(E);
-    const QLearnKernel k = E->slip.on ? qlearn_kernel<true>(model, lds) : qlearn_kernel<false>(model, lds);
-    return launch_episode(E, k, lds ? kRollWave * roll_stride(E->HWp) : 0, TraceBufs{q.tr_state, q.tr_act, q.trace_len}, q,
-                          explore_args(E), slip_args(E));
-}
-
-int launch_q_greedy(mgdp_envs *E, int32_t model, int S, const double *d_Q, int32_t n_act, int8_t *d_pi, double *d_Vq) {
-    const long long n = (long long)E->B * S;
-    auto k = model == MGDP_MODEL_XYD ? envs_q_greedy_kernel<7> : envs_q_greedy_kernel<5>;
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (int rc = timing_pair(E, ta, tb)) return rc;
-    hipExtLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, E->stream, ta, tb, 0, n, d_Q, n_act, d_pi, d_Vq);
-    MGDP_HIP(hipGetLastError());
-    return 0;
-}
-
-}  // namespace
+#include "envs_host.h"
+#include "envs_host_state.h"
+#include "envs_host_episode.h"
 
 extern "C" {
 
@@ -740,6 +457,7 @@ int mgdp_envs_create(int32_t device, int32_t B, int32_t W, int32_t H, int32_t vi
         MGDP_CHECK(roll_reader != -2, MGDP_E_INVALID, "MGDP_ROLLOUT_READER must be hbm or lds (got %s)", ev);
     }
     DeviceGuard guard(device);
+    MGDP_CHECK(guard.ok, MGDP_E_HIP, "hipSetDevice(%d) failed", device);
     mgdp_envs *E = new mgdp_envs();
     E->group = group;
     E->roll_reader = roll_reader;
@@ -776,11 +494,10 @@ int mgdp_envs_destroy(mgdp_envs *E) {
     DeviceGuard guard(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     void *ps[] = {E->d_cell, E->d_see, E->d_agent, E->d_carry, E->d_max, E->d_act,
-                  E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->d_stage,
-                  E->d_roll, E->slip.state, E->slip.half, E->explore.state, E->explore.half, E->d_stream_mask};
+                  E->d_dir, E->d_status, E->d_obs, E->d_term, E->d_trunc, E->d_rew, E->d_cont, E->d_ccont, E->stage.p,
+                  E->roll.p, E->slip.state, E->slip.half, E->explore.state, E->explore.half, E->d_stream_mask};
     for (void *p : ps) (void)hipFree(p);
-    for (auto &p : E->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &p : E->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    E->timed.destroy();
     if (E->own_stream) (void)hipStreamDestroy(E->stream);
     delete E;
     return 0;
@@ -805,101 +522,11 @@ int mgdp_envs_set_stream(mgdp_envs *E, void *s) {
     return 0;
 }
 
-// A masked reset (mgdp_envs_load with a mask): the host packs every env's prepared record into one
-// staging buffer, one copy takes it to the device, and this kernel writes the masked envs' cells,
-// agent, carry, max_steps and see_through and clears their Box contents -- O(1) runtime calls for
-// any number of envs (a per-env copy / memset loop made a 65536-env auto-reset ~300k API calls).
-// Staging layout: [mask B][see B][pad to 16][cells B*HWp][agent B*4 i32][carry B*2 i32][max B i32].
-__global__ void __launch_bounds__(64)
-envs_masked_load_kernel(int B, int HWp, const uint8_t *__restrict__ st, uint8_t *__restrict__ cell, int32_t *__restrict__ agent,
-                        int32_t *__restrict__ carry, int32_t *__restrict__ maxs, uint8_t *__restrict__ see,
-                        uint8_t *__restrict__ cont, uint8_t *__restrict__ ccont) {
-    const int b = blockIdx.x;
-    if (!st[b]) return;
-    const size_t o_cells = (size_t)((2 * B + 15) / 16 * 16);
-    const uint4 *src = reinterpret_cast<const uint4 *>(st + o_cells + (size_t)b * HWp);
-    uint4 *dst = reinterpret_cast<uint4 *>(cell + (size_t)b * HWp);
-    for (int i = threadIdx.x; i < HWp / 16; i += blockDim.x) {
-        dst[i] = src[i];
-        if (cont) reinterpret_cast<uint4 *>(cont + (size_t)b * HWp)[i] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (threadIdx.x == 0) {
-        const int32_t *ag = reinterpret_cast<const int32_t *>(st + o_cells + (size_t)B * HWp);
-        const int32_t *cr = ag + 4 * (size_t)B;
-        const int32_t *ms = cr + 2 * (size_t)B;
-        for (int j = 0; j < 4; ++j) agent[4 * b + j] = ag[4 * b + j];
-        carry[2 * b] = cr[2 * b];
-        carry[2 * b + 1] = cr[2 * b + 1];
-        maxs[b] = ms[b];
-        see[b] = st[B + b];
-        if (ccont) ccont[b] = 0;
-    }
-}
-
 int mgdp_envs_load(mgdp_envs *E, const uint8_t *enc, const int32_t *agent, const int32_t *max_steps,
                    const uint8_t *see_through, const uint8_t *mask) {
     MGDP_CHECK(E && enc && agent && max_steps && see_through, MGDP_E_INVALID, "null argument");
     DeviceGuard guard(E->device);
-    const int B = E->B, W = E->W, H = E->H, HWp = E->HWp;
-    for (int b = 0; b < B; ++b) {
-        if (mask && !mask[b]) continue;
-        MGDP_CHECK(max_steps[b] > 0, MGDP_E_INVALID, "env %d: max_steps must be > 0", b);
-        const int x = agent[3 * b], y = agent[3 * b + 1], d = agent[3 * b + 2];
-        MGDP_CHECK(x >= 0 && y >= 0 && x < W && y < H && d >= 0 && d < 4, MGDP_E_BOUNDS,
-                   "env %d: agent (%d,%d,%d) outside the grid", b, x, y, d);
-    }
-    // x-major (W,H,3) -> row-major one-byte cell codes (cell_code); what a byte cannot hold is an
-    // encoding Grid.encode() never produces
-    std::vector<uint8_t> cl((size_t)B * HWp, (uint8_t)kCodeWall);
-    std::vector<int32_t> ag((size_t)B * 4), cr((size_t)B * 2, 0);
-    for (int b = 0; b < B; ++b) {
-        if (mask && !mask[b]) continue;
-        const uint8_t *eb = enc + (size_t)b * W * H * 3;
-        for (int x = 0; x < W; ++x)
-            for (int y = 0; y < H; ++y) {
-                const uint8_t *c = eb + (x * H + y) * 3;
-                const int t = c[0], co = t == T_EMPTY ? 0 : c[1], st = t == T_EMPTY ? 0 : c[2];
-                MGDP_CHECK(t <= T_AGENT && co <= 5 && (t == T_DOOR ? st <= D_LOCKED : st == 0), MGDP_E_INVALID,
-                           "env %d cell (%d,%d): encoding (%d,%d,%d) is not a Grid.encode() cell", b, x, y, t, c[1], c[2]);
-                cl[(size_t)b * HWp + y * W + x] = (uint8_t)cell_code(t, co, st);
-            }
-        ag[4 * b] = agent[3 * b]; ag[4 * b + 1] = agent[3 * b + 1]; ag[4 * b + 2] = agent[3 * b + 2]; ag[4 * b + 3] = 0;
-    }
-    std::vector<int32_t> ms(max_steps, max_steps + B);
-    std::vector<uint8_t> se(see_through, see_through + B);
-    if (E->d_cont && !mask) {  // new grids hold no contents until mgdp_envs_set_contents says so
-        MGDP_HIP(hipMemsetAsync(E->d_cont, 0, (size_t)B * HWp, E->stream));
-        MGDP_HIP(hipMemsetAsync(E->d_ccont, 0, (size_t)B, E->stream));
-    }
-    if (!mask) {
-        MGDP_HIP(hipMemcpyAsync(E->d_cell, cl.data(), cl.size(), hipMemcpyHostToDevice, E->stream));
-        MGDP_HIP(hipMemcpyAsync(E->d_agent, ag.data(), ag.size() * 4, hipMemcpyHostToDevice, E->stream));
-        MGDP_HIP(hipMemcpyAsync(E->d_carry, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, E->stream));
-        MGDP_HIP(hipMemcpyAsync(E->d_max, ms.data(), ms.size() * 4, hipMemcpyHostToDevice, E->stream));
-        MGDP_HIP(hipMemcpyAsync(E->d_see, se.data(), se.size(), hipMemcpyHostToDevice, E->stream));
-    } else {
-        const size_t o_cells = (size_t)((2 * B + 15) / 16 * 16);
-        const size_t need = o_cells + (size_t)B * HWp + sizeof(int32_t) * 7 * (size_t)B;
-        std::vector<uint8_t> st(need, 0);
-        std::memcpy(st.data(), mask, B);
-        std::memcpy(st.data() + B, se.data(), B);
-        std::memcpy(st.data() + o_cells, cl.data(), cl.size());
-        std::memcpy(st.data() + o_cells + (size_t)B * HWp, ag.data(), ag.size() * 4);
-        std::memcpy(st.data() + o_cells + (size_t)B * HWp + ag.size() * 4, cr.data(), cr.size() * 4);
-        std::memcpy(st.data() + o_cells + (size_t)B * HWp + ag.size() * 4 + cr.size() * 4, ms.data(), ms.size() * 4);
-        if (E->stage_bytes < need) {
-            if (E->d_stage) MGDP_HIP(hipFree(E->d_stage));
-            E->d_stage = nullptr;
-            MGDP_HIP(hipMalloc((void **)&E->d_stage, need));
-            E->stage_bytes = need;
-        }
-        MGDP_HIP(hipMemcpyAsync(E->d_stage, st.data(), need, hipMemcpyHostToDevice, E->stream));
-        hipLaunchKernelGGL(envs_masked_load_kernel, dim3(B), dim3(64), 0, E->stream, B, HWp, E->d_stage, E->d_cell,
-                           E->d_agent, E->d_carry, E->d_max, E->d_see, E->d_cont, E->d_ccont);
-        MGDP_HIP(hipGetLastError());
-    }
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return state_load(E, enc, agent, max_steps, see_through, mask);
 }
 
 int mgdp_envs_observe(mgdp_envs *E, uint8_t *obs, int32_t *direction) {
@@ -947,180 +574,39 @@ int mgdp_envs_enable_timing(mgdp_envs *E, int32_t on) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
     MGDP_HIP(hipStreamSynchronize(E->stream));
-    if (int rc = timed_collect(E)) return rc;  // drop launches timed before this call
-    E->timing = on != 0;
-    E->total_ms = 0.0;
-    E->launches = 0;
-    return 0;
+    return E->timed.restart(on != 0);  // drops launches timed before this call
 }
 
 int mgdp_envs_kernel_time(mgdp_envs *E, double *total_ms, int64_t *launches) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
     MGDP_HIP(hipStreamSynchronize(E->stream));
-    if (int rc = timed_collect(E)) return rc;
-    if (total_ms) *total_ms = E->total_ms;
-    if (launches) *launches = (int64_t)E->launches;
-    return 0;
+    return E->timed.read(total_ms, launches);
 }
 
 int mgdp_envs_get_state(mgdp_envs *E, uint8_t *enc, int32_t *agent, int32_t *carry, int32_t *step_count) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
-    const int B = E->B, W = E->W, H = E->H, HWp = E->HWp;
-    std::vector<int32_t> ag((size_t)B * 4);
-    MGDP_HIP(hipMemcpyAsync(ag.data(), E->d_agent, ag.size() * 4, hipMemcpyDeviceToHost, E->stream));
-    if (carry) MGDP_HIP(hipMemcpyAsync(carry, E->d_carry, 8 * (size_t)B, hipMemcpyDeviceToHost, E->stream));
-    std::vector<uint8_t> cl;
-    if (enc) {
-        cl.resize((size_t)B * HWp);
-        MGDP_HIP(hipMemcpyAsync(cl.data(), E->d_cell, cl.size(), hipMemcpyDeviceToHost, E->stream));
-    }
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    for (int b = 0; b < B; ++b) {
-        if (agent) { agent[3 * b] = ag[4 * b]; agent[3 * b + 1] = ag[4 * b + 1]; agent[3 * b + 2] = ag[4 * b + 2]; }
-        if (step_count) step_count[b] = ag[4 * b + 3];
-        if (enc) {
-            uint8_t *eb = enc + (size_t)b * W * H * 3;
-            for (int x = 0; x < W; ++x)
-                for (int y = 0; y < H; ++y) {
-                    const size_t i = (size_t)b * HWp + y * W + x;
-                    uint8_t *c = eb + (x * H + y) * 3;
-                    int t, co, st;
-                    cell_decode(cl[i], t, co, st);
-                    c[0] = (uint8_t)t; c[1] = (uint8_t)co; c[2] = (uint8_t)st;
-                }
-        }
-    }
-    return 0;
+    return state_get(E, enc, agent, carry, step_count);
 }
 
 int mgdp_envs_set_state(mgdp_envs *E, const int32_t *agent, const int32_t *carry, const int32_t *step_count,
                         const uint8_t *mask) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
-    const int B = E->B;
-    std::vector<int32_t> ag((size_t)B * 4), cr((size_t)B * 2);
-    std::vector<uint8_t> cc((carry && E->d_ccont) ? (size_t)B : 0);  // carried Box contents
-    MGDP_HIP(hipMemcpyAsync(ag.data(), E->d_agent, ag.size() * 4, hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipMemcpyAsync(cr.data(), E->d_carry, cr.size() * 4, hipMemcpyDeviceToHost, E->stream));
-    if (!cc.empty()) MGDP_HIP(hipMemcpyAsync(cc.data(), E->d_ccont, cc.size(), hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    for (int b = 0; b < B; ++b) {
-        if (mask && !mask[b]) continue;
-        if (agent) {
-            MGDP_CHECK(agent[3 * b] >= 0 && agent[3 * b] < E->W && agent[3 * b + 1] >= 0 && agent[3 * b + 1] < E->H &&
-                           agent[3 * b + 2] >= 0 && agent[3 * b + 2] < 4,
-                       MGDP_E_BOUNDS, "env %d: agent outside the grid", b);
-            ag[4 * b] = agent[3 * b]; ag[4 * b + 1] = agent[3 * b + 1]; ag[4 * b + 2] = agent[3 * b + 2];
-        }
-        if (step_count) ag[4 * b + 3] = step_count[b];
-        if (carry) {
-            cr[2 * b] = carry[2 * b]; cr[2 * b + 1] = carry[2 * b + 1];
-            if (!cc.empty()) cc[b] = 0;  // a new carry holds nothing (see mgdp_envs_set_contents)
-        }
-    }
-    MGDP_HIP(hipMemcpyAsync(E->d_agent, ag.data(), ag.size() * 4, hipMemcpyHostToDevice, E->stream));
-    MGDP_HIP(hipMemcpyAsync(E->d_carry, cr.data(), cr.size() * 4, hipMemcpyHostToDevice, E->stream));
-    if (!cc.empty()) MGDP_HIP(hipMemcpyAsync(E->d_ccont, cc.data(), cc.size(), hipMemcpyHostToDevice, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return state_set(E, agent, carry, step_count, mask);
 }
 
-// Box(contains=...) (world_object.py:272-294): toggle puts the held object in the box's cell,
-// pickup carries the box with it, drop puts it back.  Contents are (type, colour, state) triples in
-// Grid.encode() layout, type <= 1 (unseen / empty) = nothing held; each must be a cell code (see
-// cell_code) and sit on a Box cell of the current grid; a carried one needs a carried Box.
 int mgdp_envs_set_contents(mgdp_envs *E, const uint8_t *contents, const int32_t *carry_contents) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
-    const int B = E->B, W = E->W, H = E->H, HWp = E->HWp;
-    std::vector<uint8_t> cl((size_t)B * HWp);
-    std::vector<int32_t> cr((size_t)B * 2);
-    MGDP_HIP(hipMemcpyAsync(cl.data(), E->d_cell, cl.size(), hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipMemcpyAsync(cr.data(), E->d_carry, cr.size() * 4, hipMemcpyDeviceToHost, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    auto code_of = [](int t, int c, int s, uint8_t &out) -> bool {  // a held object's cell code
-        if (t <= T_EMPTY) { out = 0; return true; }
-        if (t == T_AGENT || c > 5 || (t == T_DOOR ? s > D_LOCKED : s != 0)) return false;
-        out = (uint8_t)cell_code(t, c, s);
-        return true;
-    };
-    std::vector<uint8_t> co, cc;
-    if (contents) {
-        co.assign((size_t)B * HWp, 0);
-        for (int b = 0; b < B; ++b)
-            for (int x = 0; x < W; ++x)
-                for (int y = 0; y < H; ++y) {
-                    const uint8_t *c = contents + ((size_t)b * W * H + x * H + y) * 3;
-                    uint8_t code;
-                    MGDP_CHECK(code_of(c[0], c[1], c[2], code), MGDP_E_INVALID,
-                               "env %d cell (%d,%d): contents (%d,%d,%d) is not an object encoding", b, x, y, c[0], c[1], c[2]);
-                    const size_t i = (size_t)b * HWp + y * W + x;
-                    int t, col, st;
-                    cell_decode(cl[i], t, col, st);
-                    MGDP_CHECK(code == 0 || t == T_BOX, MGDP_E_INVALID, "env %d cell (%d,%d): contents on a non-box cell", b, x, y);
-                    co[i] = code;
-                }
-    }
-    if (carry_contents) {
-        cc.assign((size_t)B, 0);
-        for (int b = 0; b < B; ++b) {
-            const int32_t *c = carry_contents + 3 * b;
-            uint8_t code;
-            MGDP_CHECK(c[0] >= 0 && c[1] >= 0 && c[2] >= 0 && code_of(c[0], c[1], c[2], code), MGDP_E_INVALID,
-                       "env %d: carried contents (%d,%d,%d) is not an object encoding", b, c[0], c[1], c[2]);
-            MGDP_CHECK(code == 0 || cr[2 * b] == T_BOX, MGDP_E_INVALID, "env %d: contents for a carried non-box", b);
-            cc[b] = code;
-        }
-    }
-    if (!E->d_cont) {
-        hipError_t e = hipMalloc((void **)&E->d_cont, (size_t)B * HWp);
-        if (e == hipSuccess) e = hipMalloc((void **)&E->d_ccont, (size_t)B);
-        if (e == hipSuccess) e = hipMemsetAsync(E->d_cont, 0, (size_t)B * HWp, E->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(E->d_ccont, 0, (size_t)B, E->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(E->d_cont);
-            (void)hipFree(E->d_ccont);
-            E->d_cont = E->d_ccont = nullptr;
-            return hip_fail(e, "mgdp_envs_set_contents allocation", __FILE__, __LINE__);
-        }
-    }
-    if (contents) MGDP_HIP(hipMemcpyAsync(E->d_cont, co.data(), co.size(), hipMemcpyHostToDevice, E->stream));
-    if (carry_contents) MGDP_HIP(hipMemcpyAsync(E->d_ccont, cc.data(), cc.size(), hipMemcpyHostToDevice, E->stream));
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return contents_set(E, contents, carry_contents);
 }
 
 int mgdp_envs_get_contents(mgdp_envs *E, uint8_t *contents, int32_t *carry_contents) {
     MGDP_CHECK(E, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(E->device);
-    const int B = E->B, W = E->W, H = E->H, HWp = E->HWp;
-    std::vector<uint8_t> co((size_t)B * HWp, 0), cc((size_t)B, 0);
-    if (E->d_cont) {
-        MGDP_HIP(hipMemcpyAsync(co.data(), E->d_cont, co.size(), hipMemcpyDeviceToHost, E->stream));
-        MGDP_HIP(hipMemcpyAsync(cc.data(), E->d_ccont, cc.size(), hipMemcpyDeviceToHost, E->stream));
-        MGDP_HIP(hipStreamSynchronize(E->stream));
-    }
-    auto put = [](uint8_t code, int &t, int &c, int &s) {
-        if (code == 0) { t = c = s = 0; return; }
-        cell_decode(code, t, c, s);
-    };
-    for (int b = 0; b < B; ++b) {
-        int t, c, s;
-        if (contents)
-            for (int x = 0; x < W; ++x)
-                for (int y = 0; y < H; ++y) {
-                    put(co[(size_t)b * HWp + y * W + x], t, c, s);
-                    uint8_t *o = contents + ((size_t)b * W * H + x * H + y) * 3;
-                    o[0] = (uint8_t)t; o[1] = (uint8_t)c; o[2] = (uint8_t)s;
-                }
-        if (carry_contents) {
-            put(cc[b], t, c, s);
-            carry_contents[3 * b] = t; carry_contents[3 * b + 1] = c; carry_contents[3 * b + 2] = s;
-        }
-    }
-    return 0;
+    return contents_get(E, contents, carry_contents);
 }
 
 // ---- policy lookup and fused rollout ---------------------------------------
@@ -1152,16 +638,7 @@ int mgdp_envs_policy_actions(mgdp_envs *E, int32_t model, const int8_t *pi, int3
     if (int rc = roll_check(E, model, pi, T, &S)) return rc;
     MGDP_CHECK(actions, MGDP_E_INVALID, "null argument");
     DeviceGuard guard(E->device);
-    const size_t B = E->B, n_pi = (size_t)T * B * S;
-    RollCursor c;
-    const size_t o_pi = c.take(n_pi);
-    if (int rc = roll_scratch(E, c.end)) return rc;
-    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
-    MGDP_HIP(hipMemcpyAsync(d_pi, pi, n_pi, hipMemcpyHostToDevice, E->stream));
-    if (int rc = launch_policy_actions(E, model, d_pi, T, S, E->d_act, E->d_status)) return rc;
-    if (download(E, actions, E->d_act, 4 * B) || download(E, status, E->d_status, 4 * B)) return MGDP_E_HIP;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return policy_actions_host(E, model, pi, T, S, actions, status);
 }
 
 int mgdp_envs_rollout(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, int32_t n_max, int32_t *steps, double *ret,
@@ -1173,22 +650,7 @@ int mgdp_envs_rollout(mgdp_envs *E, int32_t model, const int8_t *pi, int32_t T, 
     TraceBufs h;  // the caller's buffers; none: no trace is taken
     if (int rc = trace_host(trace_state, trace_action, trace_len, &h)) return rc;
     DeviceGuard guard(E->device);
-    const size_t B = E->B, n_pi = (size_t)T * B * S, n_tr = (size_t)h.len * B;
-    RollCursor c;
-    const size_t o_pi = c.take(n_pi), o_ts = c.take(4 * n_tr), o_ta = c.take(n_tr);
-    if (int rc = roll_scratch(E, c.end)) return rc;
-    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
-    const TraceBufs d{roll_at<int32_t>(E, o_ts), roll_at<int8_t>(E, o_ta), h.len};
-    MGDP_HIP(hipMemcpyAsync(d_pi, pi, n_pi, hipMemcpyHostToDevice, E->stream));
-    // the step entry points' per-env buffers serve as outputs: d_act holds the step counts
-    const RolloutArgs r{d_pi, T, S, n_max, d.len, E->d_act, E->d_rew, E->d_term, E->d_trunc, E->d_status, d.state, d.act};
-    if (int rc = launch_rollout(E, model, r)) return rc;
-    if (download(E, steps, E->d_act, 4 * B) || download(E, ret, E->d_rew, 8 * B) || download(E, terminated, E->d_term, B) ||
-        download(E, truncated, E->d_trunc, B) || download(E, status, E->d_status, 4 * B) ||
-        download(E, h.state, d.state, 4 * n_tr) || download(E, h.act, d.act, n_tr))
-        return MGDP_E_HIP;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return rollout_host(E, model, pi, T, S, n_max, steps, ret, terminated, truncated, status, h);
 }
 
 // ---- slip: per-env PCG64 action noise ---------------------------------------
@@ -1270,24 +732,9 @@ int mgdp_envs_q_learn(mgdp_envs *E, int32_t model, double *Q, int32_t n_steps, d
     TraceBufs h;  // the caller's buffers; none: no trace is taken
     if (int rc = trace_host(trace_state, trace_action, trace_len, &h)) return rc;
     DeviceGuard guard(E->device);
-    // scratch: Q | episodes | wins | trace states | trace actions; steps, ret and status use the step buffers
-    const size_t B = E->B, n_q = sizeof(double) * B * S * A, n_tr = (size_t)h.len * B;
-    RollCursor c;
-    const size_t o_q = c.take(n_q), o_ep = c.take(4 * B), o_wn = c.take(4 * B), o_ts = c.take(4 * n_tr), o_ta = c.take(n_tr);
-    if (int rc = roll_scratch(E, c.end)) return rc;
-    double *d_Q = roll_at<double>(E, o_q);
-    int32_t *d_ep = roll_at<int32_t>(E, o_ep), *d_wn = roll_at<int32_t>(E, o_wn);
-    const TraceBufs d{roll_at<int32_t>(E, o_ts), roll_at<int8_t>(E, o_ta), h.len};
-    MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
-    const QLearnArgs q{d_Q, S, n_steps, n_act, unit_goal, d.len, alpha, gamma, eps, E->d_act, d_ep, d_wn,
-                       E->d_rew, E->d_status, d.state, d.act};
-    if (int rc = launch_qlearn(E, model, q)) return rc;
-    if (download(E, Q, d_Q, n_q) || download(E, steps, E->d_act, 4 * B) || download(E, episodes, d_ep, 4 * B) ||
-        download(E, wins, d_wn, 4 * B) || download(E, ret, E->d_rew, 8 * B) || download(E, status, E->d_status, 4 * B) ||
-        download(E, h.state, d.state, 4 * n_tr) || download(E, h.act, d.act, n_tr))
-        return MGDP_E_HIP;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    const QLearnArgs q{nullptr, S, n_steps, n_act, unit_goal, 0, alpha, gamma, eps, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr};
+    return q_learn_host(E, model, q, A, Q, steps, episodes, wins, ret, status, h);
 }
 
 int mgdp_envs_q_greedy_device(mgdp_envs *E, int32_t model, const double *d_Q, int32_t n_act, int8_t *d_pi, double *d_Vq) {
@@ -1303,17 +750,8 @@ int mgdp_envs_q_greedy(mgdp_envs *E, int32_t model, const double *Q, int32_t n_a
     if (int rc = q_model_check(E, model, n_act, &S, &A)) return rc;
     MGDP_CHECK(Q && pi, MGDP_E_INVALID, "null argument");
     DeviceGuard guard(E->device);
-    const size_t n = (size_t)E->B * S, n_q = sizeof(double) * n * A, n_v = sizeof(double) * n;
-    RollCursor c;
-    const size_t o_q = c.take(n_q), o_v = c.take(n_v), o_pi = c.take(n);
-    if (int rc = roll_scratch(E, c.end)) return rc;
-    double *d_Q = roll_at<double>(E, o_q), *d_V = roll_at<double>(E, o_v);
-    int8_t *d_pi = roll_at<int8_t>(E, o_pi);
-    MGDP_HIP(hipMemcpyAsync(d_Q, Q, n_q, hipMemcpyHostToDevice, E->stream));
-    if (int rc = launch_q_greedy(E, model, S, d_Q, n_act, d_pi, Vq ? d_V : nullptr)) return rc;
-    if (download(E, pi, d_pi, n) || download(E, Vq, d_V, n_v)) return MGDP_E_HIP;
-    MGDP_HIP(hipStreamSynchronize(E->stream));
-    return 0;
+    return q_greedy_host(E, model, S, A, Q, n_act, pi, Vq);
 }
 
 }  // extern "C"
+

@@ -60,6 +60,7 @@
 
 #include "common.h"
 #include "comm.h"
+#include "timed.h"
 
 #include "vi_plan.h"
 #include "vi_rule.h"
@@ -239,8 +240,7 @@ int mgdp_vi_destroy(mgdp_vi *vi) {
     DeviceGuard guard(vi->d.device);
     (void)server_stop(vi);
     if (vi->stream) (void)hipStreamSynchronize(vi->stream);
-    for (auto &p : vi->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &p : vi->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    vi->timed.destroy();
     for (void *p : {(void *)vi->d_cells, vi->d_V[0], vi->d_V[1], (void *)vi->d_pi, (void *)vi->d_kenv, (void *)vi->d_kexec,
                     (void *)vi->d_order, (void *)vi->d_dvenv, (void *)vi->d_shards, (void *)vi->d_red, (void *)vi->d_pub1,
                     (void *)vi->d_gk, (void *)vi->d_breq, vi->d_rgoal, (void *)vi->d_pi_t, (void *)vi->d_eval,
@@ -795,10 +795,7 @@ int mgdp_vi_enable_timing(mgdp_vi *vi, int32_t on) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(vi->d.device);
     if (int rc = drain(vi)) return rc;
-    if (int rc = timed_collect(vi)) return rc;  // drop launches timed before this call
-    vi->timing = on != 0;
-    vi->total_ms = 0.0;
-    vi->launches = 0;
+    if (int rc = vi->timed.restart(on != 0)) return rc;
     vi->clk_cycles = vi->clk_ticks = vi->clk_busy = vi->clk_solves = 0.0;
     vi->clk_launches = 0;
     return 0;
@@ -833,10 +830,7 @@ int mgdp_vi_kernel_time(mgdp_vi *vi, double *total_ms, int64_t *launches) {
     MGDP_CHECK(vi, MGDP_E_INVALID, "null handle");
     DeviceGuard guard(vi->d.device);
     if (int rc = drain(vi)) return rc;
-    if (int rc = timed_collect(vi)) return rc;
-    if (total_ms) *total_ms = vi->total_ms;
-    if (launches) *launches = vi->launches;
-    return 0;
+    return vi->timed.read(total_ms, launches);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // vi_host.h -- the value-iteration handle: struct mgdp_vi (the ABI's opaque handle) and ViKernels, the
-// kernel arguments made of it (make_geo, make_coef), the pooled event pairs of timed launches, the clock
+// kernel arguments made of it (make_geo, make_coef), the clock
 // of departed servers, the epoch of a host-published launch, and the check of a cells array against the
 // model.  Part of the single translation unit vi.hip: included after the device headers, first of the
 // host pieces (vi_host.h, vi_host_launch.h, vi_host_serve.h, vi_host_order.h, vi_host_eval.h,
@@ -46,12 +46,8 @@ struct mgdp_vi {
     int k_done = 0;     // sweeps completed by every grid (uniform after run_to / sweep)
     int32_t sweeps = 0, converged = 0;
     bool cells_loaded = false;
-    // timing of the dominant kernel
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, ev_pool;
-    std::vector<int> ev_sweep;  // sweep index of each timed sweep launch (-1 = fused launch)
-    double total_ms = 0.0;
-    int64_t launches = 0;
+    // timing of the dominant kernel (timed.h); a pair's tag: the sweep index of a timed sweep launch, -1 = fused launch
+    TimedPool timed;
     int fresh = 1;          // next fused launch starts from V_0 = 0
     unsigned int epoch = 0; // tag of the last fused launch; its result lands in h_out[0..3]
     // what runs (vi_plan.h): the MGDP_* knobs, the plan made of them at create, the plan's kernels
@@ -149,44 +145,6 @@ Coef<T> make_coef(const mgdp_vi *vi) {
     c.tol = t;
     c.dc = (T)vi->d.death_cost;
     return c;
-}
-
-// Timed launches go through hipExtLaunchKernelGGL with a start/stop event pair, so the events carry
-// the dispatch's own begin/end timestamps (what rocprofv3's kernel trace reports) rather than the
-// times of separate marker packets.  Event pairs are pooled: no hipEventCreate in the timed loop.
-struct TimedPair { hipEvent_t a = nullptr, b = nullptr; };
-int timed_begin(mgdp_vi *vi, int sweep_idx, TimedPair *tp) {
-    tp->a = tp->b = nullptr;
-    if (!vi->timing) return 0;
-    std::pair<hipEvent_t, hipEvent_t> e;
-    if (!vi->ev_pool.empty()) {
-        e = vi->ev_pool.back();
-        vi->ev_pool.pop_back();
-    } else {
-        MGDP_HIP(hipEventCreate(&e.first));
-        MGDP_HIP(hipEventCreate(&e.second));
-    }
-    vi->ev.push_back(e);
-    vi->ev_sweep.push_back(sweep_idx);
-    tp->a = e.first;
-    tp->b = e.second;
-    return 0;
-}
-// Fold completed events into total_ms (called after a stream sync).  Sweep launches past the
-// stopping sweep no-op and were marked uncounted (ev_sweep = INT_MAX) by sweep_run.
-int timed_collect(mgdp_vi *vi) {
-    for (size_t i = 0; i < vi->ev.size(); ++i) {
-        if (vi->ev_sweep[i] != INT32_MAX) {
-            float ms = 0.f;
-            MGDP_HIP(hipEventElapsedTime(&ms, vi->ev[i].first, vi->ev[i].second));
-            vi->total_ms += ms;
-            vi->launches += 1;
-        }
-        vi->ev_pool.push_back(vi->ev[i]);
-    }
-    vi->ev.clear();
-    vi->ev_sweep.clear();
-    return 0;
 }
 
 // Add a departed server's clock words (written before its exit word, which is a release) once.

@@ -70,7 +70,7 @@ int launch_per_grid(mgdp_vi *vi, K kern, int block, int lds, Args... args) {
     const EvalShape s = eval_shape(vi->HW, vi->HWp, vi->S, vi->tsize);
     if (lds > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    if (int rc = vi->timed.begin(-1, &tp)) return rc;
     hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(block), lds, vi->stream, tp.a, tp.b, 0, eval_geo(vi, s), args...);
     return 0;
 }

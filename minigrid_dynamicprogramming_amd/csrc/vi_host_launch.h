@@ -37,7 +37,7 @@ int launch_opts_t(mgdp_vi *vi, int k_target) {
     auto kern = vi_fused_opts_kernel<T, MODEL, SLIP, ND, HMODE>;
     if (L.total() > 64 * 1024) MGDP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total()));
     TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    if (int rc = vi->timed.begin(-1, &tp)) return rc;
     hipExtLaunchKernelGGL(kern, dim3(vi->d.B), dim3(vi->plan.block), L.total(), vi->stream, tp.a, tp.b, 0, g,
                           make_coef<T>(vi), vi->d_cells, (T *)vi->d_V[0], vi->d_pi, vi->d_kenv, vi->d_dvenv,
                           vi->d_red, vi->d_ticket, vi->d_hout, k_target, vi->fresh,
@@ -168,7 +168,7 @@ int launch_fused_t(mgdp_vi *vi, int k_target, unsigned long long *pub, const lon
         std::fprintf(stderr, "mgdp occupancy: %d workgroups/CU (block %d, LDS %d B)\n", per_cu, block, smem);
     }
     TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    if (int rc = vi->timed.begin(-1, &tp)) return rc;
     // the in-launch reduction (GkCtx): a fresh own-rule launch of a resident one-wave batch folds
     // each grid's {k_e, dV at k_e} through the counter tree and publishes {kmax, dV, kmin} itself (no
     // reduce kernel); grids at an exact fixed point are complete for any K (fixed-point completion),
@@ -195,7 +195,7 @@ int launch_serve_t(mgdp_vi *vi, unsigned int served) {
     MGDP_CHECK(!batch || vi->k.bserve, MGDP_E_INVALID, "batch server: not a one-wave deterministic XYD batch");
     const Geo g = make_geo(vi);
     TimedPair tp;
-    if (int rc = timed_begin(vi, -1, &tp)) return rc;
+    if (int rc = vi->timed.begin(-1, &tp)) return rc;
     account_server_clock(vi);  // a server that left on its own (idle / life limit) before this relaunch
     ++vi->serve_tag;
     if (batch) {
@@ -266,7 +266,7 @@ int launch_sweep_t(mgdp_vi *vi, int k, int check_prev, bool policy) {
     T *Vout = (T *)vi->d_V[k & 1];
     if (policy) return launch_sweep_kernel<T, MODEL, SLIP, MAP, true>(vi, Vin, Vout, k, 0);
     TimedPair tp;
-    if (int rc = timed_begin(vi, k, &tp)) return rc;
+    if (int rc = vi->timed.begin(k, &tp)) return rc;
     if constexpr (MAP == MGDP_MAP_CELL) {
         if (vi->plan.sweep_pipe == 1) return launch_sweep_pipe<T, MODEL, SLIP, 1>(vi, Vin, Vout, k, check_prev, tp);
         if (vi->plan.sweep_pipe == 2) return launch_sweep_pipe<T, MODEL, SLIP, 2>(vi, Vin, Vout, k, check_prev, tp);

@@ -138,7 +138,7 @@ bool serve_eligible(const mgdp_vi *vi) { return vi->kn.persistent && vi->plan.se
 // launch), from V_0 = 0 under the own rule with at least one sweep.  Its buffers exist only where
 // the plan wants a batch server and it has a resident capacity.
 bool bserve_eligible(const mgdp_vi *vi) {
-    return vi->kn.persistent && vi->d_breq && vi->d_gk && !vi->timing && vi->d.B > 1 &&
+    return vi->kn.persistent && vi->d_breq && vi->d_gk && !vi->timed.on && vi->d.B > 1 &&
            (vi->d.B <= vi->plan.bserve_cap || vi->plan.bserve_any) &&
            !vi->plan.opts && vi->d.method == MGDP_METHOD_FUSED && vi->d.horizon == 0 && vi->d.max_sweeps >= 1;
 }
@@ -253,7 +253,7 @@ int sweep_run(mgdp_vi *vi, int k_stop, bool force, double *dv_out) {
     std::vector<unsigned long long> host(8 * chunk);
     double dv = 0.0;
     while (vi->k_done < k_stop) {
-        const size_t ev0 = vi->ev_sweep.size();
+        const size_t ev0 = vi->timed.tag.size();
         const int n = std::min(chunk, k_stop - vi->k_done);
         for (int i = 1; i <= n; ++i)
             if (int rc = dispatch<SweepF>(vi, vi->k_done + i, force ? 0 : 1, false)) return rc;
@@ -269,8 +269,8 @@ int sweep_run(mgdp_vi *vi, int k_stop, bool force, double *dv_out) {
                 break;
             }
         }
-        for (size_t i = ev0; i < vi->ev_sweep.size(); ++i)
-            if (vi->ev_sweep[i] > last) vi->ev_sweep[i] = INT32_MAX;
+        for (size_t i = ev0; i < vi->timed.tag.size(); ++i)  // sweeps past the stopping one no-op: not counted
+            if (vi->timed.tag[i] > last) vi->timed.tag[i] = TimedPool::kUncounted;
         vi->k_done = last;
         vi->cur = last & 1;
         if (stop) break;

@@ -196,3 +196,47 @@ def test_masked_load_replaces_only_masked_envs():
     np.testing.assert_array_equal(rew[m], rrew)
     ref.close()
     venv.close()
+
+
+def test_masked_load_on_a_non_square_grid_with_contents():
+    """B=3, W=5, H=4 (a transposed or mis-padded walk moves cells; HW = 20, HWp = 32), mask [1, 0, 1], a Box
+    with contents in env 1 and in env 2: after the masked load env 1's grid and contents are untouched,
+    envs 0 and 2 hold the new cells and no contents -- cell by cell through get_state / get_contents."""
+    B, W, H = 3, 5, 4
+
+    def grids(seed_colour):
+        enc = np.zeros((B, W, H, 3), np.uint8)
+        enc[..., 0] = 1
+        enc[:, 0, :] = enc[:, -1, :] = enc[:, :, 0] = enc[:, :, -1] = (2, 5, 0)
+        for b in range(B):  # every inner cell its own object, so that no two cells of a grid are equal
+            for n, (x, y) in enumerate((x, y) for x in range(1, W - 1) for y in range(1, H - 1)):
+                enc[b, x, y] = ((5, 6, 3, 4, 9, 8)[n], (seed_colour + b + n) % 6, 2 if n == 3 else 0)
+        return enc
+
+    enc0, enc1 = grids(0), grids(3)
+    enc0[1, 2, 1] = (7, 1, 0)
+    enc0[2, 3, 2] = (7, 4, 0)
+    held0 = np.zeros_like(enc0)
+    held0[1, 2, 1] = (5, 2, 0)   # env 1: a Box holding a key
+    held0[2, 3, 2] = (4, 3, 2)   # env 2: a Box holding a locked door
+    agent = np.tile(np.array([1, 1, 0], np.int32), (B, 1))
+    agent1 = np.tile(np.array([3, 2, 1], np.int32), (B, 1))
+    venv = MiniGridVecEnv("MiniGrid-DistShift1-v0", B, width=W, height=H)
+    assert (venv.W, venv.H) == (W, H)
+    venv.load(enc0, agent, max_steps=[9] * B, see_through=[False] * B, held=held0)
+    st = venv.get_state()
+    np.testing.assert_array_equal(st["enc"], enc0)
+    np.testing.assert_array_equal(st["held"], held0)
+    mask = np.array([1, 0, 1], np.uint8)
+    venv.load(enc1, agent1, max_steps=[7] * B, see_through=[True] * B, mask=mask)
+    st = venv.get_state()
+    held, carry_held = venv.get_contents()
+    for b in range(B):
+        new = bool(mask[b])
+        for x in range(W):
+            for y in range(H):
+                assert tuple(st["enc"][b, x, y]) == tuple((enc1 if new else enc0)[b, x, y]), (b, x, y)
+                assert tuple(held[b, x, y]) == ((0, 0, 0) if new else tuple(held0[b, x, y])), (b, x, y)
+        assert tuple(st["agent"][b]) == tuple((agent1 if new else agent)[b])
+    assert not carry_held.any()
+    venv.close()
