@@ -279,3 +279,8 @@ def ptr(a) -> ctypes.c_void_p:
     if hasattr(a, "data_ptr"):
         return ctypes.c_void_p(a.data_ptr())
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def dev_ptr(x) -> ctypes.c_void_p | None:
+    """A device address given as an int (e.g. a torch tensor's data_ptr()) as a pointer argument; None stays None."""
+    return None if x is None else ctypes.c_void_p(int(x))

@@ -7,10 +7,13 @@ of two scalars over RCCL/xGMI (backend "nccl" on ROCm) or gloo on CPU:
 
     k_r, e_r = run_local()             each grid sweeps until its own |dV| < tol (no communication);
                                        e_r = max |dV| of the shard's grids at their own last sweeps
-    K, E  = allreduce_max(k_r, e_r)    the slowest grid anywhere, and the largest own-rule dV
+    K, E  = link.kd(k_r, e_r)          the slowest grid anywhere, and the largest own-rule dV
     dv_r  = run_to(K)                  every grid advanced to exactly K sweeps
-    dv    = 0 if E == 0 else allreduce_max(dv_r)
-    while dv >= tol and K < max_sweeps:  dv = allreduce_max(sweep()); K += 1   (rare fallback)
+    dv    = 0 if E == 0 else link.dv_at_k(dv_r)
+    while dv >= tol and K < max_sweeps:  dv = link.sweep_dv(sweep()); K += 1   (rare fallback)
+
+A link is the three MAX all-reduces with their read-back over one transport: _ReducerLink over a Reducer's int64
+protocol words (torch.distributed), _CommLink over a LibComm (the library's own collectives).
 
 Each grid's Jacobi trajectory V_0, V_1, ... does not depend on the other grids, so after this
 protocol every grid holds exactly the V_K / pi_K that one global loop would produce.  The Bellman
@@ -155,10 +158,6 @@ class Reducer:
         return self.device_ms
 
 
-# kept for callers of the round-1 name
-_Reducer = Reducer
-
-
 class LibComm:
     """The library's own communicator (mgdp_comm_*, include/mgdp.h ABI 11): RCCL over xGMI called
     from libmgdp, so a sharded solve is ONE C call per rank (mgdp_vi_solve_sharded) with its
@@ -279,21 +278,54 @@ class LibComm:
             pass
 
 
-def _lib_host_protocol(vi, comm):
-    """The collectives of mgdp_vi_solve_sharded driven from the host, for a rank whose shard cannot
-    run it (EmptyShard, sweep method, DP options): {k_r, own-rule dV bits} (2 words), then dV(K)
-    (1 word) only if the all-reduced dV bits are non-zero -- same words, same order as the C side."""
-    vi.reset()
-    k_loc, e_loc = _local(vi)
-    K, e_bits = comm.allreduce_max([int(k_loc), double_to_bits(e_loc)])
-    k = int(K)
-    dv = vi.run_to(k)
-    if bits_to_double(e_bits) == 0.0:
-        if dv != 0.0:
-            raise RuntimeError(f"fixed-point invariant violated: dV at sweep {k} is {dv!r}")
-    else:
-        dv = bits_to_double(comm.allreduce_max([double_to_bits(dv)])[0])
-    return k, dv
+class _ReducerLink:
+    """The link over a Reducer: {k, own-rule dV bits} in red.proto[0:2] and dV at K in red.proto[5], MAX
+    all-reduced in place and read back -- the device protocol's tensors, dtypes and order, so ranks on either
+    path meet in the same collectives; a fallback sweep's dV through red.max (the float64 scalar)."""
+    __slots__ = ("red",)
+
+    def __init__(self, red):
+        self.red = red
+
+    def _max_read(self, words):
+        red = self.red
+        red.max_(words)
+        t = time.perf_counter()
+        host = words.tolist()
+        red.wall_s += time.perf_counter() - t
+        red.host_reads += 1
+        return host
+
+    def kd(self, k, e):
+        red = self.red
+        red.proto[0:2].copy_(red.torch.tensor([int(k), double_to_bits(e)], dtype=red.torch.int64))
+        K, e_bits = self._max_read(red.p_kd)
+        return int(K), bits_to_double(e_bits)
+
+    def dv_at_k(self, dv):
+        self.red.p_dv.fill_(double_to_bits(dv))
+        return bits_to_double(self._max_read(self.red.p_dv)[0])
+
+    def sweep_dv(self, dv):
+        return self.red.max(dv)
+
+
+class _CommLink:
+    """The link over a LibComm, for a rank whose shard cannot run mgdp_vi_solve_sharded: {k, own-rule dV bits}
+    (2 words), dV at K (1 word), one word per fallback sweep -- same words, same order as the C side."""
+    __slots__ = ("comm",)
+
+    def __init__(self, comm):
+        self.comm = comm
+
+    def kd(self, k, e):
+        K, e_bits = self.comm.allreduce_max([int(k), double_to_bits(e)])
+        return int(K), bits_to_double(e_bits)
+
+    def dv_at_k(self, dv):
+        return bits_to_double(self.comm.allreduce_max([double_to_bits(dv)])[0])
+
+    sweep_dv = dv_at_k
 
 
 class EmptyShard:
@@ -350,7 +382,6 @@ def _device_capable(vi, red) -> bool:
 
 
 def _device_protocol(vi, red):
-    p = red.proto
     vi.reset()
     vi.run_local_dev(red.p_local)         # {k max, own-rule dV bits, k min, 0}
     red.max_(red.p_kd)                    # K = the slowest grid anywhere, E = the largest own-rule dV
@@ -363,43 +394,23 @@ def _device_protocol(vi, red):
             raise RuntimeError(f"fixed-point invariant violated: dV at sweep {k} is {dv!r} after an exact "
                                "fixed point on every rank")
     else:
-        red.p_dv.fill_(double_to_bits(dv))
-        red.max_(red.p_dv)                # dV at K over every rank
-        t = time.perf_counter()
-        dv = bits_to_double(int(p[5].item()))
-        red.wall_s += time.perf_counter() - t
-        red.host_reads += 1
+        dv = _ReducerLink(red).dv_at_k(dv)  # dV at K over every rank (slip): the link's second operation
     vi.set_result(k, dv)
     return k, dv
 
 
-def _host_protocol(vi, red):
-    """The device protocol's collectives, driven from the host: {k_r, own-rule dV bits} into
-    red.proto[0:2], MAX all-reduce, read back; run_to(K); dV at K through red.proto[5] unless every
-    grid everywhere stopped at an exact fixed point.  Same tensors, dtypes and order as
-    _device_protocol, so ranks on either path meet in the same collectives."""
-    p = red.proto
+def _host_protocol(vi, link):
+    """The protocol above up to dV at K, driven from the host over `link` (either transport; a shard that cannot
+    take the device path next to peers that do)."""
     vi.reset()
     k_loc, e_loc = _local(vi)
-    p[0:2].copy_(red.torch.tensor([int(k_loc), double_to_bits(e_loc)], dtype=red.torch.int64))
-    red.max_(red.p_kd)
-    t = time.perf_counter()
-    K, e_bits = red.p_kd.tolist()
-    red.wall_s += time.perf_counter() - t
-    red.host_reads += 1
-    k = int(K)
+    k, rule = link.kd(k_loc, e_loc)
     dv = vi.run_to(k)
-    if bits_to_double(e_bits) == 0.0:
+    if rule == 0.0:                       # every grid everywhere at an exact fixed point: dV(K) = 0, no collective
         if dv != 0.0:
             raise RuntimeError(f"fixed-point invariant violated: dV at sweep {k} is {dv!r}")
-    else:
-        red.p_dv.fill_(double_to_bits(dv))
-        red.max_(red.p_dv)
-        t = time.perf_counter()
-        dv = bits_to_double(int(p[5].item()))
-        red.wall_s += time.perf_counter() - t
-        red.host_reads += 1
-    return k, dv
+        return k, dv
+    return k, link.dv_at_k(dv)
 
 
 def _local(vi):
@@ -422,36 +433,39 @@ def solve_sharded(vi, group=None, reducer=None, comm=None) -> dict:
         n0, w0 = comm.allreduces, comm.host_waits
         if getattr(vi, "sharded_capable", False):
             k = vi.solve_sharded(comm)
-            return {"sweeps": k, "dv": vi.dv, "converged": vi.converged, "allreduces": comm.allreduces - n0,
-                    "host_reads": comm.host_waits - w0, "protocol": "lib"}
-        k, dv = _lib_host_protocol(vi, comm)
-        while not (dv < vi.tol) and k < vi.max_sweeps:
-            dv = bits_to_double(comm.allreduce_max([double_to_bits(vi.sweep())])[0])
-            k += 1
-        vi.finish(k, dv)
-        return {"sweeps": k, "dv": dv, "converged": dv < vi.tol, "allreduces": comm.allreduces - n0,
-                "host_reads": comm.host_waits - w0, "protocol": "lib-host"}
-    red = reducer or Reducer(group)
-    device = _device_capable(vi, red)
-    calls0, reads0 = red.calls, red.host_reads
-    if device:
-        if red.stream is not None:
-            vi.bind_stream(red.stream_ptr)
-            prev = red.enter_stream()
-            try:
-                k, dv = _device_protocol(vi, red)
-            finally:
-                red.exit_stream(prev)
-        else:
-            k, dv = _device_protocol(vi, red)
+            return _result(k, vi.dv, vi.converged, comm.allreduces - n0, comm.host_waits - w0, "lib")
+        protocol, link = "lib-host", _CommLink(comm)
+        k, dv = _host_protocol(vi, link)
     else:
-        k, dv = _host_protocol(vi, red)
+        red = reducer or Reducer(group)
+        n0, w0 = red.calls, red.host_reads
+        if _device_capable(vi, red):
+            protocol, link = "device", None  # the deterministic path needs no link: made where one is used
+            if red.stream is not None:
+                vi.bind_stream(red.stream_ptr)
+                prev = red.enter_stream()
+                try:
+                    k, dv = _device_protocol(vi, red)
+                finally:
+                    red.exit_stream(prev)
+            else:
+                k, dv = _device_protocol(vi, red)
+        else:
+            protocol, link = "host", _ReducerLink(red)
+            k, dv = _host_protocol(vi, link)
     while not (dv < vi.tol) and k < vi.max_sweeps:
-        dv = red.max(vi.sweep())
+        link = link or _ReducerLink(red)
+        dv = link.sweep_dv(vi.sweep())
         k += 1
     vi.finish(k, dv)
-    return {"sweeps": k, "dv": dv, "converged": dv < vi.tol, "allreduces": red.calls - calls0,
-            "host_reads": red.host_reads - reads0, "protocol": "device" if device else "host"}
+    if comm is not None:
+        return _result(k, dv, dv < vi.tol, comm.allreduces - n0, comm.host_waits - w0, protocol)
+    return _result(k, dv, dv < vi.tol, red.calls - n0, red.host_reads - w0, protocol)
+
+
+def _result(sweeps, dv, converged, allreduces, host_reads, protocol) -> dict:
+    return {"sweeps": sweeps, "dv": dv, "converged": converged, "allreduces": allreduces, "host_reads": host_reads,
+            "protocol": protocol}
 
 
 def gather_results(V: np.ndarray, group=None):

@@ -19,7 +19,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from . import checkpoint as _ckpt
 from .core import COLOR_TO_IDX, OBJECT_TO_IDX
 
 MODELS = {"xyd": _lib.MODEL_XYD, "doorkey": _lib.MODEL_DOORKEY}
@@ -250,7 +251,7 @@ class ValueIteration:
         self.h = h
         _LIVE.add(self)
         if stream is not None:
-            _lib.check(self.L.mgdp_vi_set_stream(h, ctypes.c_void_p(int(stream))), "mgdp_vi_set_stream")
+            _lib.check(self.L.mgdp_vi_set_stream(h, _lib.dev_ptr(stream)), "mgdp_vi_set_stream")
         self.load(cells)
 
     @property
@@ -298,7 +299,7 @@ class ValueIteration:
         its next request, so this makes no HIP call; the bytes are not validated here."""
         if self._load_dev_fn is None:
             self._load_dev_fn = _lib.raw_fn("mgdp_vi_load_cells_device")
-        rc = self._load_dev_fn(self.h, ctypes.c_void_p(int(cells_ptr)))
+        rc = self._load_dev_fn(self.h, _lib.dev_ptr(cells_ptr))
         if rc:
             _lib.check(rc, "mgdp_vi_load_cells_device")
         self._cells_digest = None  # not read back: a checkpoint of these grids cannot be verified
@@ -341,29 +342,6 @@ class ValueIteration:
         return self._out[0].value
 
     # -- policy evaluation / improvement / policy iteration (DESIGN.md sections 13 and 19)
-    def _check_policy(self, pi) -> np.ndarray:
-        """(B, S) int8 action lanes (any integer dtype that fits), checked before any device work."""
-        return self._check_policy_opts(pi, rows=False)[0]
-
-    def _check_policy_opts(self, pi, rows: bool = True) -> tuple[np.ndarray, int]:
-        """_check_policy that with `rows` also takes (H, B, S) on a finite-horizon handle: (array, rows T)."""
-        a = np.asarray(pi)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
-        rows = rows and self.horizon > 0
-        if a.shape == (self.B, self.S):
-            T = 1
-        elif rows and a.shape == (self.horizon, self.B, self.S):
-            T = self.horizon
-        else:
-            want = f"{(self.B, self.S)}" + (f" or {(self.horizon, self.B, self.S)}" if rows else "")
-            raise ValueError(f"policy of shape {a.shape} does not match the handle's {want}")
-        if a.dtype != np.int8:
-            if a.size and (a.min() < -128 or a.max() > 127):
-                raise ValueError("policy entries do not fit int8 action lanes")
-            a = a.astype(np.int8)
-        return np.ascontiguousarray(a), T
-
     def _call_result(self, name: str, *args) -> int:
         """`name`(handle, *args, &sweeps, &dv, &converged): the three become the handle's result."""
         k, dv, conv = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_int32(0)
@@ -372,11 +350,10 @@ class ValueIteration:
         return self.sweeps
 
     def _call_policy_iteration(self, name: str, pi0, max_iters) -> dict:
-        a = None if pi0 is None else self._check_policy(pi0)
-        if int(max_iters) <= 0:
-            raise ValueError("max_iters must be > 0")
+        a = None if pi0 is None else _args.evaluate_policy(pi0, self.B, self.S)[0]
+        max_iters = _args.max_iters(max_iters)
         it, tot, ch, dv = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
-        _lib.check(getattr(self.L, name)(self.h, None if a is None else _lib.ptr(a), int(max_iters), ctypes.byref(it),
+        _lib.check(getattr(self.L, name)(self.h, None if a is None else _lib.ptr(a), max_iters, ctypes.byref(it),
                                          ctypes.byref(tot), ctypes.byref(ch), ctypes.byref(dv)), name)
         # converged of the last evaluation: dv < tol unless max_sweeps capped it
         self.dv = dv.value
@@ -391,14 +368,14 @@ class ValueIteration:
         valid state raises ValueError naming grid and state.  Returns the sweeps of the global
         stopping rule; values(), policy(), grid_sweeps() and result() then describe the evaluation.
         run_to / sweep / resume need a reset() afterwards; solve() works as before."""
-        a = self._check_policy(pi)
+        a, _ = _args.evaluate_policy(pi, self.B, self.S)
         return self._call_result("mgdp_vi_evaluate", _lib.ptr(a))
 
     def evaluate_device(self, pi_ptr: int | None = None) -> int:
         """evaluate() of a policy in device memory (mgdp_vi_evaluate_device): B*S int8 at `pi_ptr`
         (16-byte aligned, e.g. a torch int8 tensor's data_ptr()); None evaluates the handle's own pi
         buffer -- pi* right after a solve()."""
-        return self._call_result("mgdp_vi_evaluate_device", None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)))
+        return self._call_result("mgdp_vi_evaluate_device", _lib.dev_ptr(pi_ptr))
 
     def improve(self) -> int:
         """Greedy improvement on the handle's V (mgdp_vi_improve): pi(s) <- argmax_a Q(s, a), lowest
@@ -422,9 +399,8 @@ class ValueIteration:
         step); values() is then V_0, policy() the normalised pi_0, and with values_t=True values_t()
         returns every V_t as (H, B, S).  A lane outside [0, A) on a valid state, in any row, raises
         ValueError naming grid, t and state.  On a plain handle: exactly evaluate().  Returns the sweeps."""
-        a, T = self._check_policy_opts(pi)
-        if values_t and self.horizon == 0:
-            raise ValueError("values_t needs a finite horizon")
+        a, T = _args.evaluate_policy(pi, self.B, self.S, self.horizon, rows=True)
+        _args.values_t_horizon(values_t, self.horizon)
         vt = np.empty((self.horizon, self.B, self.S), self.np_dtype) if values_t else None
         self._values_t = None
         k = self._call_result("mgdp_vi_evaluate_opts", _lib.ptr(a), T, None if vt is None else _lib.ptr(vt))
@@ -442,14 +418,9 @@ class ValueIteration:
         """evaluate_opts() with the policy (T*B*S int8, T = 1 or the horizon) and optionally V_t (H*B*S of
         the handle's dtype) in device memory, 16-byte aligned (mgdp_vi_evaluate_opts_device).  pi_ptr None:
         the handle's own pi (T = 1) or pi_t (T = horizon, needs keep_policy_t) -- pi_t* right after solve()."""
-        T = int(T)
-        if T != 1 and not (self.horizon > 0 and T == self.horizon):
-            raise ValueError(f"policy rows T = {T}: 1 or the handle's horizon ({self.horizon})")
-        if values_t_ptr is not None and self.horizon == 0:
-            raise ValueError("values_t needs a finite horizon")
+        T = _args.evaluate_rows(T, values_t_ptr is not None, self.horizon)
         self._values_t = None
-        return self._call_result("mgdp_vi_evaluate_opts_device", None if pi_ptr is None else ctypes.c_void_p(int(pi_ptr)),
-                                 T, None if values_t_ptr is None else ctypes.c_void_p(int(values_t_ptr)))
+        return self._call_result("mgdp_vi_evaluate_opts_device", _lib.dev_ptr(pi_ptr), T, _lib.dev_ptr(values_t_ptr))
 
     def improve_opts(self) -> int:
         """improve() on a plain or lava="nodeath" handle (mgdp_vi_improve_opts); refused on a finite horizon."""
@@ -463,32 +434,6 @@ class ValueIteration:
         return self._call_policy_iteration("mgdp_vi_policy_iteration_opts", pi0, max_iters)
 
     # -- the forward pass of a policy
-    def _occupancy_steps(self, n_steps) -> int:
-        if self.horizon > 0:
-            if n_steps is not None and int(n_steps) != self.horizon:
-                raise ValueError(f"n_steps = {n_steps} on a finite-horizon handle: None or the horizon {self.horizon}")
-            return self.horizon
-        if n_steps is None:
-            raise ValueError("n_steps is required on a horizon-0 handle")
-        return int(n_steps)
-
-    def _occupancy_policy(self, pi, N: int) -> tuple[np.ndarray, int]:
-        a = np.asarray(pi)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
-        if a.shape == (self.B, self.S):
-            T = 1
-        elif a.shape == (N, self.B, self.S):
-            T = N
-        else:
-            raise ValueError(f"policy of shape {a.shape} does not match {(self.B, self.S)} or {(N, self.B, self.S)}"
-                             f" (rows T = {a.shape[0] if a.ndim == 3 else '?'})")
-        if a.dtype != np.int8:
-            if a.size and (a.min() < -128 or a.max() > 127):
-                raise ValueError("policy entries do not fit int8 action lanes")
-            a = a.astype(np.int8)
-        return np.ascontiguousarray(a), T
-
     def occupancy(self, pi, start, n_steps: int | None = None, every_step: bool = False) -> OccupancyResult:
         """The forward pass mu_{t+1} = P_pi^T mu_t of a policy (mgdp_vi_occupancy): exactly N steps, N the
         horizon on a finite-horizon handle and n_steps otherwise.  pi is (B, S) or (N, B, S) int8 lanes (row t
@@ -498,16 +443,9 @@ class ValueIteration:
         a lane outside [0, 7) on a valid state (naming grid, the smallest such t, and state), a start index out
         of range or on a wall / goal / terminal lava, mu_0 mass on one of those, rows other than 1 or N, a
         DoorKey handle.  every_step=True also returns every mu_t as (N, B, S)."""
-        N = self._occupancy_steps(n_steps)
-        a, T = self._occupancy_policy(pi, N)
-        st = np.asarray(start)
-        s_idx = mu0 = None
-        if st.shape == (self.B,) and st.dtype.kind in "iu":
-            s_idx = np.ascontiguousarray(np.clip(st.astype(np.int64), -1, 2 ** 31 - 1), np.int32)
-        elif st.shape == (self.B, self.S):
-            mu0 = np.ascontiguousarray(st, self.np_dtype)
-        else:
-            raise ValueError(f"start of shape {st.shape} is neither {(self.B,)} state indices nor a {(self.B, self.S)} array")
+        N = _args.occupancy_steps(n_steps, self.horizon)
+        a, T = _args.occupancy_policy(pi, self.B, self.S, N)
+        s_idx, mu0 = _args.occupancy_start(start, self.B, self.S, self.np_dtype)
         mu, occ, ret = (np.empty((self.B, self.S), self.np_dtype) for _ in range(3))
         mu_t = np.empty((N, self.B, self.S), self.np_dtype) if every_step else None
         _lib.check(self.L.mgdp_vi_occupancy(self.h, _lib.ptr(a), T, _lib.ptr(s_idx), _lib.ptr(mu0), N, _lib.ptr(mu),
@@ -522,11 +460,8 @@ class ValueIteration:
         """occupancy() on device memory (mgdp_vi_occupancy_device), on the handle's stream: the policy (T*B*S
         int8, T = 1 or N), start (B int32) or mu0 (B*S), and the outputs mu (required), occ, ret (B*S) and
         mu_t (N*B*S) of the handle's dtype, 16-byte aligned (start: 4).  Returns N; the results are complete."""
-        N = self._occupancy_steps(n_steps)
-
-        def p(x):
-            return None if x is None else ctypes.c_void_p(int(x))
-
+        N = _args.occupancy_steps(n_steps, self.horizon)
+        p = _lib.dev_ptr
         _lib.check(self.L.mgdp_vi_occupancy_device(self.h, p(pi_ptr), int(T), p(start_ptr), p(mu0_ptr), N, p(mu_ptr),
                                                    p(occ_ptr), p(ret_ptr), p(mu_t_ptr)), "mgdp_vi_occupancy_device")
         return N
@@ -555,16 +490,14 @@ class ValueIteration:
         """action_values() into device memory (mgdp_vi_action_values_device), on the handle's stream: Q (B*S*A of
         the handle's dtype) at q_ptr and / or opt (B*S uint8) at opt_ptr, 16-byte aligned (e.g. torch tensors'
         data_ptr()); either may be None, not both.  The results are complete when it returns."""
-        def p(x):
-            return None if x is None else ctypes.c_void_p(int(x))
-
+        p = _lib.dev_ptr
         _lib.check(self.L.mgdp_vi_action_values_device(self.h, p(q_ptr), p(opt_ptr)), "mgdp_vi_action_values_device")
 
     def is_optimal(self, pi) -> np.ndarray:
         """(B, S) bool: whether pi's lane is a maximising action of the handle's V, whichever it chose among ties;
         True on walls and absorbing states (whatever their entry), False where a valid state's lane is outside
         [0, A).  pi as evaluate() takes it."""
-        a = self._check_policy(pi)
+        a, _ = _args.evaluate_policy(pi, self.B, self.S)
         opt = self.optimal_actions()
         lane = a.astype(np.int64)
         inr = (lane >= 0) & (lane < n_actions(self.model))
@@ -651,7 +584,7 @@ class ValueIteration:
     def bind_stream(self, stream_ptr: int):
         """Launch on this hipStream_t from now on (no-op when it already does)."""
         if getattr(self, "_bound_stream", None) != int(stream_ptr):
-            _lib.check(self.L.mgdp_vi_set_stream(self.h, ctypes.c_void_p(int(stream_ptr))), "mgdp_vi_set_stream")
+            _lib.check(self.L.mgdp_vi_set_stream(self.h, _lib.dev_ptr(stream_ptr)), "mgdp_vi_set_stream")
             self._bound_stream = int(stream_ptr)
 
     def run_local_dev(self, pub):
@@ -735,43 +668,11 @@ class ValueIteration:
         Refused (ValueError): a converged checkpoint (final), V of another shape or dtype, a
         checkpoint of other grids or parameters (its "meta"), and with verify_cells a handle or
         checkpoint whose cells are unknown (loaded with load_device)."""
-        meta = ckpt.get("meta")
-        if meta is None:
-            raise ValueError("checkpoint has no meta (grids and parameters); refusing to resume blind")
-        mine = self._ckpt_meta()
-        for key, val in mine.items():
-            if key == "cells_sha256":
-                continue
-            if meta.get(key) != val:
-                raise ValueError(f"checkpoint {key}={meta.get(key)!r} does not match the handle's {val!r}")
-        if verify_cells:
-            if mine["cells_sha256"] is None or meta.get("cells_sha256") is None:
-                raise ValueError("cells digest unknown (load_device); pass verify_cells=False to resume anyway")
-            if meta["cells_sha256"] != mine["cells_sha256"]:
-                raise ValueError("checkpoint was taken on other grids (cells sha256 differs)")
-        V = np.asarray(ckpt["V"])
-        if V.dtype != self.np_dtype:
-            raise ValueError(f"checkpoint V is {V.dtype}, the handle computes in {np.dtype(self.np_dtype)}")
-        if V.shape != (self.B, self.S):
-            raise ValueError(f"checkpoint V of shape {V.shape} does not match the handle's {(self.B, self.S)}")
-        V = np.ascontiguousarray(V)
+        V = _ckpt.resume_values(self._ckpt_meta(), ckpt, self.np_dtype, self.B, self.S, verify_cells)
         return self._call_result("mgdp_vi_resume", _lib.ptr(V), int(ckpt["sweeps"]), float(ckpt["dv"]))
 
-    @staticmethod
-    def save_checkpoint(path, ckpt: dict) -> None:
-        """Write a checkpoint as .npz (plain arrays and a JSON string: np.load needs no pickle)."""
-        import json
-
-        np.savez(path, V=ckpt["V"], pi=ckpt["pi"], sweeps=np.int64(ckpt["sweeps"]), dv=np.float64(ckpt["dv"]),
-                 converged=np.bool_(ckpt["converged"]), meta=np.str_(json.dumps(ckpt.get("meta"))))
-
-    @staticmethod
-    def load_checkpoint(path) -> dict:
-        import json
-
-        z = np.load(path)  # allow_pickle=False
-        return {"V": z["V"], "pi": z["pi"], "sweeps": int(z["sweeps"]), "dv": float(z["dv"]),
-                "converged": bool(z["converged"]), "meta": json.loads(str(z["meta"])) if "meta" in z else None}
+    save_checkpoint = staticmethod(_ckpt.save_checkpoint)
+    load_checkpoint = staticmethod(_ckpt.load_checkpoint)
 
     def dv_trace(self) -> np.ndarray:
         t = np.zeros(self.sweeps, np.float64)
@@ -835,19 +736,12 @@ class ValueIteration:
         return self.B * self.S * n_actions(self.model)
 
 
-def _has_options(kwargs) -> bool:
-    return bool(kwargs.get("horizon", 0)) or kwargs.get("lava", "terminal") == "nodeath"
-
-
 def policy_evaluation(grids, pi, **kwargs) -> VIResult:
     """V^pi of one policy per grid ((B, S) int8, see ValueIteration.evaluate) on one GPU; kwargs as
     ValueIteration (gamma, tol, slip_p, dtype, ...).  The result's pi is the evaluated policy."""
     vi = ValueIteration(grids, **kwargs)
     try:
-        if _has_options(kwargs):  # horizon / NoDeath: DESIGN.md section 19 ((H, B, S) accepted with a horizon)
-            vi.evaluate_opts(pi)
-        else:
-            vi.evaluate(pi)
+        vi.evaluate_opts(pi)  # any handle (DESIGN.md section 19): (H, B, S) accepted with a horizon
         return vi.result()
     finally:
         vi.close()
@@ -870,10 +764,8 @@ def action_values(grids, pi=None, **kwargs) -> ActionValues:
     try:
         if pi is None:
             vi.solve()
-        elif _has_options(kwargs):
-            vi.evaluate_opts(pi)
         else:
-            vi.evaluate(pi)
+            vi.evaluate_opts(pi)
         Q, opt = vi.action_values(optimal=True)
         return ActionValues(Q, opt, vi.values(), vi.policy(), vi.sweeps, vi.model)
     finally:
@@ -885,7 +777,7 @@ def policy_iteration(grids, pi0=None, max_iters: int = 1000, **kwargs) -> VIResu
     eval_sweeps and changed, and its sweeps is the last evaluation's count."""
     vi = ValueIteration(grids, **kwargs)
     try:
-        r = (vi.policy_iteration_opts if _has_options(kwargs) else vi.policy_iteration)(pi0, max_iters=max_iters)
+        r = vi.policy_iteration_opts(pi0, max_iters=max_iters)
         out = vi.result()
         out.iters, out.eval_sweeps, out.changed = r["iters"], r["eval_sweeps"], r["changed"]
         return out

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib, gen
+from . import _args, _lib, gen
 from .registry import make
 
 
@@ -244,9 +244,9 @@ class MiniGridVecEnv:
             raise ValueError(f"unknown model {model!r}")
         return model
 
-    def _policy_args(self, policy, model):
+    def _policy_of(self, policy, model):
         """(pi int8 (T*B, S) contiguous, T, model id) of a (B, S) / (T, B, S) integer array or a VIResult,
-        checked before any device work (as ValueIteration._check_policy)."""
+        checked before any device work (_args.rollout_policy)."""
         from . import dp
 
         if isinstance(policy, dp.VIResult):
@@ -254,37 +254,14 @@ class MiniGridVecEnv:
                 model = policy.model
             policy = policy.pi
         model = self._model_of(model, "rollout / policy_actions")
-        a = np.asarray(policy)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"policy must be an integer array (int8 action lanes), got dtype {a.dtype}")
-        B, S = self.num_envs, dp.n_states(model, self.W, self.H)
-        if a.shape != (B, S) and (a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (B, S)):
-            raise ValueError(f"policy of shape {a.shape} is neither {(B, S)} nor (T, {B}, {S}) of the {model} model")
-        if a.dtype != np.int8:
-            if a.size and (a.min() < -128 or a.max() > 127):
-                raise ValueError("policy entries do not fit int8 action lanes")
-            a = a.astype(np.int8)
-        T = 1 if a.ndim == 2 else a.shape[0]
-        if a.ndim == 3 and T == 1:
-            raise ValueError("a time-indexed policy needs T > 1 rows; pass (B, S) for a stationary one")
-        return np.ascontiguousarray(a), T, dp.MODELS[model]
-
-    def _trace_arrays(self, trace, full_len, cap):
-        """(states int32 (n, B), actions int8 (n, B), n) for trace=True (n = full_len) or a number of steps,
-        at most cap rows (0: no cap); (None, None, 0) for no trace."""
-        if not trace:
-            return None, None, 0
-        n = full_len if trace is True else int(trace)
-        if n <= 0:
-            raise ValueError("trace must be True, False or a positive number of steps")
-        n = min(n, cap) if cap else n
-        return np.empty((n, self.num_envs), np.int32), np.empty((n, self.num_envs), np.int8), n
+        pi, T = _args.rollout_policy(policy, self.num_envs, dp.n_states(model, self.W, self.H), model)
+        return pi, T, dp.MODELS[model]
 
     def policy_actions(self, policy, model: str = "auto", return_status: bool = False):
         """(B,) int32: the env action `policy` takes at every env's current state (mgdp_envs_policy_actions),
         -1 where it has none (a lane outside the model's, a grid or carry outside the model, step_count
         beyond a time-indexed policy); return_status also gives the per-env status."""
-        pi, T, mid = self._policy_args(policy, model)
+        pi, T, mid = self._policy_of(policy, model)
         acts = np.zeros(self.num_envs, np.int32)
         status = np.zeros(self.num_envs, np.int32)
         _lib.check(self.L.mgdp_envs_policy_actions(self.h, mid, _lib.ptr(pi), T, _lib.ptr(acts), _lib.ptr(status)),
@@ -301,16 +278,14 @@ class MiniGridVecEnv:
         to the envs' max_steps rows of B entries each are allocated), trace=n those of the first n steps.
         A later call continues where this one stopped.  After set_slip() every step's action first passes
         the env's slip stream; the trace then holds the executed actions."""
-        pi, T, mid = self._policy_args(policy, model)
+        pi, T, mid = self._policy_of(policy, model)
         B = self.num_envs
-        n_max = 0 if max_steps is None else int(max_steps)
-        if max_steps is not None and n_max <= 0:
-            raise ValueError("max_steps must be > 0 (None: no budget)")
+        n_max = _args.rollout_budget(max_steps)
         steps, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
         ret = np.zeros(B, np.float64)
         term, trunc = np.zeros(B, np.uint8), np.zeros(B, np.uint8)
         # no env outlives its max_steps from step_count 0; a budget bounds it further
-        ts, ta, tlen = self._trace_arrays(trace, max(int(self._ms_cap), 1), n_max)
+        ts, ta, tlen = _args.trace_arrays(trace, max(int(self._ms_cap), 1), n_max, B)
         _lib.check(self.L.mgdp_envs_rollout(self.h, mid, _lib.ptr(pi), T, n_max, _lib.ptr(steps), _lib.ptr(ret),
                                             _lib.ptr(term), _lib.ptr(trunc), _lib.ptr(status), _lib.ptr(ts), _lib.ptr(ta),
                                             tlen), "mgdp_envs_rollout")
@@ -347,15 +322,6 @@ class MiniGridVecEnv:
             _lib.check(rc, "mgdp_envs_rollout_device")
 
     # ---------------------------------------------------------------- slip
-    def _seed_args(self, seed, mask):
-        """(seed int, mask uint8 (B,) or None) of a seeding of one stream per env, slip or explore."""
-        seed = int(seed)
-        if not 0 <= seed <= 2**64 - self.num_envs:
-            raise ValueError(f"seed .. seed + {self.num_envs} must fit 64 bits (one SeedSequence entropy int each)")
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask).reshape(self.num_envs), np.uint8)
-        return seed, mask
-
     def _read_streams(self, fn, name):
         """The records that `fn` (a stream table's getter) copies out, as slip_streams() documents them."""
         B = self.num_envs
@@ -373,10 +339,8 @@ class MiniGridVecEnv:
         draw of the env actions 0..5 (None).  mask (B,): reseed only those envs' streams (prob and
         random_action always hold for the whole handle); the first call must seed them all.  step(),
         policy_actions(), load() and reset() neither draw nor touch the streams (mgdp_envs_set_slip)."""
-        seed, m = self._seed_args(seed, mask)
-        ra = -1 if random_action is None else int(random_action)
-        if random_action is not None and ra < 0:
-            raise ValueError(f"random_action must be an env action 0..6 or None, got {random_action}")
+        seed, m = _args.seed_args(seed, mask, self.num_envs)
+        ra = _args.slip_random_action(random_action)
         _lib.check(self.L.mgdp_envs_set_slip(self.h, float(prob), ra, seed, _lib.ptr(m)), "mgdp_envs_set_slip")
 
     def clear_slip(self):
@@ -407,45 +371,17 @@ class MiniGridVecEnv:
 
     # ---------------------------------------------------------------- tabular Q-learning
     def _q_model(self, model, n_act):
-        """(model name, model id, S, A, n_act) checked before any device work, in the style of _policy_args."""
+        """(model name, model id, S, A, n_act) checked before any device work."""
         from . import dp
 
         model = self._model_of(model, "q_learn / q_greedy")
         S, A = dp.n_states(model, self.W, self.H), dp.n_actions(model)
-        n_act = A if n_act is None else int(n_act)
-        if not 1 <= n_act <= A:
-            raise ValueError(f"n_act must be in 1..{A} for the {model} model, got {n_act}")
-        return model, dp.MODELS[model], S, A, n_act
-
-    def _q_table(self, Q, S, A):
-        B = self.num_envs
-        if Q is None:
-            return np.zeros((B, S, A), np.float64)
-        q = np.asarray(Q)
-        if q.dtype != np.float64:
-            raise ValueError(f"Q must be float64 (fp32 tables are out of scope), got dtype {q.dtype}")
-        if q.shape != (B, S, A):
-            raise ValueError(f"Q of shape {q.shape} is not {(B, S, A)}")
-        return np.array(q, np.float64, order="C")  # the caller's table stays as it is
-
-    @staticmethod
-    def _q_params(n_steps, alpha, gamma, eps):
-        n_steps = int(n_steps)
-        if n_steps <= 0:
-            raise ValueError(f"n_steps must be > 0, got {n_steps}")
-        if n_steps >= 2**31:
-            raise ValueError("n_steps must fit int32")
-        alpha, gamma, eps = float(alpha), float(gamma), float(eps)
-        if not 0.0 <= eps <= 1.0:  # NaN fails both
-            raise ValueError(f"eps must be in [0, 1], got {eps}")
-        if alpha != alpha or gamma != gamma:
-            raise ValueError("alpha and gamma must not be NaN")
-        return n_steps, alpha, gamma, eps
+        return model, dp.MODELS[model], S, A, _args.q_n_act(n_act, A, model)
 
     def set_explore(self, seed: int = 0, mask=None):
         """Seed the explore streams of q_learn: env b draws from numpy.random.default_rng(seed + b).  mask
         (B,): reseed only those envs; the first call must seed them all.  Independent of the slip streams."""
-        seed, m = self._seed_args(seed, mask)
+        seed, m = _args.seed_args(seed, mask, self.num_envs)
         _lib.check(self.L.mgdp_envs_set_explore(self.h, seed, _lib.ptr(m)), "mgdp_envs_set_explore")
         self._explore = True
 
@@ -468,10 +404,10 @@ class MiniGridVecEnv:
         update stays on the chosen lane.  A per-env problem is that env's status, never an exception.
         trace=True records state and executed action of every step, trace=n of the first n."""
         model, mid, S, A, n_act = self._q_model(model, n_act)
-        n_steps, alpha, gamma, eps = self._q_params(n_steps, alpha, gamma, eps)
-        q = self._q_table(Q, S, A)
+        n_steps, alpha, gamma, eps = _args.q_params(n_steps, alpha, gamma, eps)
         B = self.num_envs
-        ts, ta, tlen = self._trace_arrays(trace, n_steps, n_steps)
+        q = _args.q_table(Q, B, S, A)
+        ts, ta, tlen = _args.trace_arrays(trace, n_steps, n_steps, B)
         if seed is not None:
             self.set_explore(seed)
         elif not self._explore:
@@ -492,7 +428,7 @@ class MiniGridVecEnv:
         (B,); the trace int32 / int8 [trace_len][B] or None.  The explore streams must have been seeded
         (set_explore, or an earlier q_learn)."""
         model, mid, S, A, n_act = self._q_model(model, n_act)
-        n_steps, alpha, gamma, eps = self._q_params(n_steps, alpha, gamma, eps)
+        n_steps, alpha, gamma, eps = _args.q_params(n_steps, alpha, gamma, eps)
         p = _lib.ptr
         rc = self.L.mgdp_envs_q_learn_device(self.h, mid, p(Q), n_steps, alpha, gamma, eps, n_act, int(bool(unit_goal)),
                                              p(steps), p(episodes), p(wins), p(ret), p(status), p(trace_state),
@@ -507,8 +443,8 @@ class MiniGridVecEnv:
         model, mid, S, A, n_act = self._q_model(model, n_act)
         if Q is None:
             raise ValueError("q_greedy needs a table")
-        q = self._q_table(Q, S, A)
         B = self.num_envs
+        q = _args.q_table(Q, B, S, A)
         pi = np.zeros((B, S), np.int8)
         vq = np.zeros((B, S), np.float64) if values else None
         _lib.check(self.L.mgdp_envs_q_greedy(self.h, mid, _lib.ptr(q), n_act, _lib.ptr(pi), _lib.ptr(vq)),

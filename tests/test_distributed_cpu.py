@@ -429,3 +429,24 @@ def test_lib_comm_protocol_matches_global_loop(world, kinds, slip):
         if hi > lo:
             np.testing.assert_array_equal(V, ref["V"][lo:hi])
             np.testing.assert_array_equal(pi, ref["pi"][lo:hi])
+
+
+class _OneRankLibComm:
+    """GlooLibComm's surface on one rank: MAX over one rank is the identity, counted as GlooLibComm counts."""
+
+    def __init__(self):
+        self.allreduces = 0
+        self.host_waits = 0
+
+    def allreduce_max(self, vals):
+        self.allreduces += 1
+        self.host_waits += 1
+        return [int(v) for v in vals]
+
+
+def test_fallback_loop_over_the_comm_link():
+    s = _NonMonotoneShard()
+    res = solve_sharded(s, comm=_OneRankLibComm())
+    assert res["sweeps"] == 5 and res["converged"] and s.final[0] == 5
+    # host-driven over the comm: {K, E} (E unknown: no local_result), dV(K), then 2 fallback sweeps
+    assert res["protocol"] == "lib-host" and res["allreduces"] == 4 and res["host_reads"] == 4

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import minigrid_dynamicprogramming_amd as mg
-from minigrid_dynamicprogramming_amd import _lib
+from minigrid_dynamicprogramming_amd import _args, _lib
 from minigrid_dynamicprogramming_amd.core import OBJECT_TO_IDX
 from oracle import oracle
 from tests import rollout_ref as rr
@@ -266,16 +266,13 @@ def test_doorkey_and_large_grids_are_refused():
 
 
 def test_front_end_refuses_bad_shapes_before_device_work():
-    vi = mg.ValueIteration.__new__(mg.ValueIteration)
-    vi.B, vi.S, vi.horizon = 2, 100, 6
-    assert vi._occupancy_steps(None) == 6 and vi._occupancy_steps(6) == 6
+    B, S, horizon = 2, 100, 6
+    assert _args.occupancy_steps(None, horizon) == 6 and _args.occupancy_steps(6, horizon) == 6
     with pytest.raises(ValueError, match="n_steps"):
-        vi._occupancy_steps(5)
-    assert vi._occupancy_policy(np.zeros((6, 2, 100), np.int64), 6)[1] == 6
+        _args.occupancy_steps(5, horizon)
+    assert _args.occupancy_policy(np.zeros((6, 2, 100), np.int64), B, S, 6)[1] == 6
     for shape in ((5, 2, 100), (2, 99)):
         with pytest.raises(ValueError, match="T ="):
-            vi._occupancy_policy(np.zeros(shape, np.int8), 6)
-    vi.horizon = 0
+            _args.occupancy_policy(np.zeros(shape, np.int8), B, S, 6)
     with pytest.raises(ValueError, match="n_steps"):
-        vi._occupancy_steps(None)
-    vi.h = None  # nothing to destroy
+        _args.occupancy_steps(None, 0)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import minigrid_dynamicprogramming_amd as mg
-from minigrid_dynamicprogramming_amd import _lib
+from minigrid_dynamicprogramming_amd import _args, _lib
 from oracle import oracle
 from tests.policy_ref import PolicyRef
 
@@ -110,14 +110,12 @@ def test_policy_iteration_slip_from_all_done():
 
 
 def test_front_end_refuses_bad_shapes_and_dtypes_before_device_work():
-    """_check_policy needs no handle state beyond B and S: shape and dtype errors are ValueError."""
-    vi = mg.ValueIteration.__new__(mg.ValueIteration)
-    vi.B, vi.S = 2, 100
+    """The policy rule needs nothing of the handle beyond B and S: shape and dtype errors are ValueError."""
+    B, S = 2, 100
     with pytest.raises(ValueError, match="shape"):
-        vi._check_policy(np.zeros((2, 99), np.int8))
+        _args.evaluate_policy(np.zeros((2, 99), np.int8), B, S)
     with pytest.raises(ValueError, match="integer"):
-        vi._check_policy(np.zeros((2, 100), np.float32))
+        _args.evaluate_policy(np.zeros((2, 100), np.float32), B, S)
     with pytest.raises(ValueError, match="int8"):
-        vi._check_policy(np.full((2, 100), 300, np.int32))
-    assert vi._check_policy(np.full((2, 100), 3, np.int64)).dtype == np.int8
-    vi.h = None  # nothing to destroy
+        _args.evaluate_policy(np.full((2, 100), 300, np.int32), B, S)
+    assert _args.evaluate_policy(np.full((2, 100), 3, np.int64), B, S)[0].dtype == np.int8

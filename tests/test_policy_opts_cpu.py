@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import minigrid_dynamicprogramming_amd as mg
-from minigrid_dynamicprogramming_amd import _lib
+from minigrid_dynamicprogramming_amd import _args, _lib
 from minigrid_dynamicprogramming_amd.core import OBJECT_TO_IDX
 from oracle import oracle
 from tests import rollout_ref as rr
@@ -221,18 +221,17 @@ def test_wrong_row_counts_are_refused():
 
 
 def test_front_end_refuses_bad_shapes_and_dtypes_before_device_work():
-    vi = mg.ValueIteration.__new__(mg.ValueIteration)
-    vi.B, vi.S, vi.horizon = 2, 100, 6
-    assert vi._check_policy_opts(np.zeros((2, 100), np.int8))[1] == 1
-    assert vi._check_policy_opts(np.zeros((6, 2, 100), np.int64))[1] == 6
+    def check(pi, horizon=6):
+        return _args.evaluate_policy(pi, 2, 100, horizon, rows=True)
+
+    assert check(np.zeros((2, 100), np.int8))[1] == 1
+    assert check(np.zeros((6, 2, 100), np.int64))[1] == 6
     for shape in ((5, 2, 100), (2, 99), (1, 2, 100)):
         with pytest.raises(ValueError, match="shape"):
-            vi._check_policy_opts(np.zeros(shape, np.int8))
+            check(np.zeros(shape, np.int8))
     with pytest.raises(ValueError, match="integer"):
-        vi._check_policy_opts(np.zeros((2, 100), np.float32))
+        check(np.zeros((2, 100), np.float32))
     with pytest.raises(ValueError, match="int8"):
-        vi._check_policy_opts(np.full((2, 100), 300, np.int32))
-    vi.horizon = 0
+        check(np.full((2, 100), 300, np.int32))
     with pytest.raises(ValueError, match="shape"):
-        vi._check_policy_opts(np.zeros((6, 2, 100), np.int8))
-    vi.h = None  # nothing to destroy
+        check(np.zeros((6, 2, 100), np.int8), horizon=0)
